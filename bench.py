@@ -15,6 +15,14 @@ kernel, table extraction + decode, cross-rank aggregate merge.
 Per-GPU work is fixed as N grows (weak scaling).
 
     python bench.py --gpus N --steps K --warmup W [--mb MB]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the one
+JSON result line.  --dump-outputs DIR also writes the aggregate the
+last timed step returned as DIR/<name>.npy; the pool is seeded, so two
+builds run with the same arguments scan identical bytes and their
+dumps compare output for output.  --full is where measurements beyond
+the headline figure belong; none exist today, so it changes nothing.
 
 For N>1 launch via torch.distributed.run with --nproc-per-node N
 (reads RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* from the env).
@@ -22,6 +30,7 @@ For N>1 launch via torch.distributed.run with --nproc-per-node N
 
 import argparse
 import json
+import multiprocessing
 import os
 import sys
 import time
@@ -33,14 +42,18 @@ def log(msg):
         sys.stderr.flush()
 
 
-def build_pool(mb, seed):
-    """Generate ~mb MB of synthetic NDJSON (mktestdata shape)."""
+SLAB_MB = 64
+
+
+def build_slab(job):
+    """One pool slab: at least `target` bytes of synthetic NDJSON
+    (mktestdata shape) from its own seed."""
+    target, seed = job
     from dragnet_amd.tools.mktestdata import generate_lines
-    target = mb * 1024 * 1024
     out = []
     total = 0
     nrec = 0
-    # generate in slabs so the record count adapts to actual line size
+    # open-ended generator so the record count adapts to actual line size
     gen = generate_lines(1 << 62, seed=seed)
     for line in gen:
         out.append(line)
@@ -49,6 +62,51 @@ def build_pool(mb, seed):
         if total >= target:
             break
     return b"".join(out), nrec
+
+
+def build_pool(mb, seed, workers=1):
+    """Generate ~mb MB of synthetic NDJSON (mktestdata shape).
+
+    The pool is a run of SLAB_MB slabs, slab i seeded (seed, i), so its
+    bytes depend on (mb, seed) alone and not on `workers`.  The
+    generator is pure Python, about a minute per GB on one core, so
+    the independent slabs are generated in parallel.  Workers are
+    forked: call this before anything initialises the GPU."""
+    target = mb * 1024 * 1024
+    nslab = max(1, -(-mb // SLAB_MB))
+    jobs = [(-(-target // nslab), (seed << 16) + i)
+            for i in range(nslab)]
+    workers = max(1, min(workers, nslab))
+    if workers == 1:
+        slabs = [build_slab(j) for j in jobs]
+    else:
+        with multiprocessing.get_context("fork").Pool(workers) as mp:
+            slabs = mp.map(build_slab, jobs, chunksize=1)
+    return b"".join(s for s, _ in slabs), sum(n for _, n in slabs)
+
+
+def dump_outputs(dirname, result):
+    """Write the aggregate a caller of the timed path receives — the
+    sorted points of the last timed step — as float64 .npy arrays:
+    point_values[i] is point i's count, point_keys[i] the UTF-8 code
+    units of its canonical-JSON `fields`, zero-padded to a common
+    width."""
+    import numpy as np
+    points = result.points()
+    keys = [json.dumps(p["fields"], sort_keys=True,
+                       separators=(",", ":")).encode("utf-8")
+            for p in points]
+    width = max([len(k) for k in keys] + [1])
+    karr = np.zeros((len(keys), width), dtype=np.float64)
+    for i, k in enumerate(keys):
+        karr[i, :len(k)] = np.frombuffer(k, dtype=np.uint8)
+    varr = np.array([p["value"] for p in points], dtype=np.float64)
+    assert karr.nbytes + varr.nbytes <= 64 << 20, \
+        "aggregate too large to dump whole"
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "point_keys.npy"), karr)
+    np.save(os.path.join(dirname, "point_values.npy"), varr)
+    log("dumped %d points to %s" % (len(points), dirname))
 
 
 def main():
@@ -67,7 +125,14 @@ def main():
     ap.add_argument("--passes", type=int, default=0,
                     help="full pool passes per step (0 = auto-size so "
                          "a step is ~150 ms of GPU work)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed "
+                         "step's aggregate as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the "
+                         "headline figure (none today)")
     args = ap.parse_args()
+    assert args.steps >= 1, "--steps must be at least 1"
 
     rank = int(os.environ.get("RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
@@ -91,6 +156,17 @@ def main():
         log("self-launching %d ranks via torch.distributed.run"
             % args.gpus)
         sys.exit(subprocess.call(cmd))
+
+    # the pool first: its generator forks workers, which must not
+    # inherit an initialised GPU runtime
+    log("generating %d MB pool per GPU ..." % args.mb)
+    t0 = time.time()
+    ncpu = len(os.sched_getaffinity(0))
+    pool, nrec = build_pool(args.mb, seed=1000 + rank,
+                            workers=max(1, min(16, ncpu) // world))
+    pool_bytes = len(pool)
+    log("pool: %d records, %.1f MB in %.1fs" % (
+        nrec, pool_bytes / 1e6, time.time() - t0))
 
     import torch
     assert torch.cuda.is_available(), "bench needs a GPU"
@@ -131,13 +207,6 @@ def main():
     query = query_load(
         filter={"eq": ["req.method", "GET"]},
         breakdown_specs="req.method,res.statusCode")
-
-    log("generating %d MB pool per GPU ..." % args.mb)
-    t0 = time.time()
-    pool, nrec = build_pool(args.mb, seed=1000 + rank)
-    pool_bytes = len(pool)
-    log("pool: %d records, %.1f MB in %.1fs" % (
-        nrec, pool_bytes / 1e6, time.time() - t0))
 
     eng = GpuEngine(device=torch.device("cuda", dev_index))
     cplan = planmod.compile_plan([query])
@@ -258,6 +327,9 @@ def main():
     # sanity: the scan actually matched records
     matched = sum(p["value"] for p in result.points())
     assert matched > 0, "no records matched the filter"
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, result)
 
     if rank == 0:
         out = {

@@ -7,6 +7,11 @@ import pytest
 REPO_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO_ROOT not in sys.path:
     sys.path.insert(0, REPO_ROOT)
+# child processes (`python -m dragnet_amd.cli`, launched ranks) import
+# the same tree whatever directory pytest was started from
+os.environ["PYTHONPATH"] = os.pathsep.join(
+    [REPO_ROOT] + [p for p in os.environ.get("PYTHONPATH", "").split(
+        os.pathsep) if p and p != REPO_ROOT])
 
 
 def pytest_configure(config):

@@ -5,24 +5,49 @@ The reference ships bash test harnesses whose `.out` files interleave
 `# dn scan <args>` marker lines with the exact expected stdout
 (tools/catest compares verbatim).  These tests parse those goldens,
 run OUR `dn` with the same arguments against the reference's own
-fixture data (/root/reference/tests/data), and require identical
-output — the strongest possible CLI-parity evidence, using goldens we
-did not produce.
+fixture data, and require identical output — the strongest possible
+CLI-parity evidence, using goldens we did not produce.
 
-Skipped when the reference checkout is not present.
+The fixture logs and the recorded `.out` files are stored under
+tests/golden/reference/, each gzipped, in the reference's own layout
+(tests/data, tests/dn/local, tests/dn/manta), and unpacked into a
+temporary tree for the module, so the replay needs nothing outside the
+repository.
 """
 
+import gzip
 import os
 import re
 import subprocess
 
 import pytest
 
-REF = "/root/reference/tests"
-DATA = os.path.join(REF, "data")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                      "golden", "reference")
+REF = None   # <unpacked tree>/tests, set by reference_tree
+DATA = None  # REF/data
 
-pytestmark = pytest.mark.skipif(
-    not os.path.isdir(DATA), reason="reference checkout not present")
+
+@pytest.fixture(scope="module", autouse=True)
+def reference_tree(tmp_path_factory):
+    """Unpack tests/golden/reference/**.gz, byte for byte, into a
+    temporary tree of the same layout."""
+    global REF, DATA
+    root = str(tmp_path_factory.mktemp("reference"))
+    nfiles = 0
+    for dirpath, _dirs, names in os.walk(GOLDEN):
+        dest = os.path.join(root, os.path.relpath(dirpath, GOLDEN))
+        os.makedirs(dest, exist_ok=True)
+        for name in names:
+            assert name.endswith(".gz"), name
+            with gzip.open(os.path.join(dirpath, name), "rb") as src, \
+                    open(os.path.join(dest, name[:-3]), "wb") as dst:
+                dst.write(src.read())
+            nfiles += 1
+    assert nfiles == 19
+    REF = os.path.join(root, "tests")
+    DATA = os.path.join(REF, "data")
+    return root
 
 
 def parse_sections(outfile):
@@ -139,7 +164,7 @@ def test_scan_fileset_goldens(dn):
     sections = parse_sections(
         os.path.join(REF, "dn", "local", "tst.scan_fileset.sh.out"))
     assert len(sections) == 38
-    prefix = os.path.dirname(REF.rstrip("/"))  # /root/reference
+    prefix = os.path.dirname(REF.rstrip("/"))  # the unpacked root
 
     assert dn("datasource-add", "test_input", "--path=" + DATA,
               "--time-format=%Y/%m-%d", "--time-field=time").code == 0
@@ -490,6 +515,9 @@ def _worker_manta_replay(rank, world, port, cfgfile, arglists, out_q):
     os.environ["MASTER_PORT"] = str(port)
     os.environ["DRAGNET_CONFIG"] = cfgfile
     os.environ["DRAGNET_ENGINE"] = "cpu"
+    # CPU ranks: gloo even where a GPU is visible (the default there
+    # is RCCL, one device per rank)
+    os.environ["DRAGNET_DIST_BACKEND"] = "gloo"
     _sys.path.insert(0, os.path.dirname(os.path.dirname(
         os.path.abspath(__file__))))
     from dragnet_amd import cli
@@ -539,6 +567,7 @@ def test_scan_manta_goldens_sharded(tmp_path):
                          args=(r, 2, 29547, cfgfile, arglists, out_q))
              for r in range(2)]
     for p in procs:
+        p.daemon = True  # a rank stuck on a dead peer dies with the run
         p.start()
     results = {}
     for _ in range(2):
@@ -686,6 +715,7 @@ def test_index_manta_goldens_sharded(tmp_path):
         args=(r, 2, 29549, cfgfile, idx_root, arglists, out_q))
         for r in range(2)]
     for p in procs:
+        p.daemon = True  # a rank stuck on a dead peer dies with the run
         p.start()
     results = {}
     for _ in range(2):
