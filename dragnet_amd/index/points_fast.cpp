@@ -191,6 +191,9 @@ bool scan_number(Cursor& c, Scalar* out) {
     char* endp = nullptr;
     long long v = strtoll(tok.c_str(), &endp, 10);
     if (errno == ERANGE || *endp != '\0') { c.fail = true; return false; }
+    // beyond 2^53 the oracle rounds to binary64 (JSON.parse): punt to
+    // the Python path rather than keep an exact int it would not see
+    if (v > (1LL << 53) || v < -(1LL << 53)) { c.fail = true; return false; }
     out->tag = Scalar::INT;
     out->i = v;
   } else {
@@ -479,7 +482,7 @@ LineWhat do_line(
                              static_cast<long long>(d));
             key_str(key, buf, static_cast<size_t>(n));
           } else {
-            return L_PUNT;  // js_num_str uses Python repr
+            return L_PUNT;  // js_num_str lays out shortest digits itself
           }
           break;
         }

@@ -28,6 +28,7 @@ matches numeric 200):
 """
 
 import math
+import re
 
 LEAF_OPS = ("eq", "ne", "lt", "le", "gt", "ge")
 _NAN = float("nan")
@@ -66,6 +67,18 @@ def _validate(pred):
         raise KrillError('"%s" value must be a scalar' % key)
 
 
+# ECMAScript WhiteSpace + LineTerminator (StrWhiteSpaceChar): what
+# Number(s) trims.  Python's str.strip() differs (it also takes
+# U+001C..U+001F and U+0085, and leaves U+FEFF).
+_JS_WS = ("\t\n\v\f\r \xa0\u1680\u2000\u2001\u2002\u2003\u2004\u2005"
+          "\u2006\u2007\u2008\u2009\u200a\u2028\u2029\u202f\u205f\u3000"
+          "\ufeff")
+
+
+_JS_DECIMAL = re.compile(
+    r"[+-]?(?:[0-9]+\.?[0-9]*|\.[0-9]+)(?:[eE][+-]?[0-9]+)?\Z")
+
+
 def to_number(v):
     """JavaScript ToNumber for the value types that can appear here."""
     if v is None:
@@ -75,7 +88,7 @@ def to_number(v):
     if isinstance(v, (int, float)):
         return float(v)
     if isinstance(v, str):
-        s = v.strip()
+        s = v.strip(_JS_WS)
         if s == "":
             return 0.0
         if s in ("Infinity", "+Infinity"):
@@ -88,6 +101,8 @@ def to_number(v):
                    "+infinity", "-infinity"):
             return _NAN
         if low.startswith("0x"):
+            if "_" in s:  # int() takes digit separators; JS does not
+                return _NAN
             try:
                 return float(int(s, 16))
             except ValueError:
@@ -96,6 +111,10 @@ def to_number(v):
             # JS Number() rejects signed hex ('-0x10' -> NaN)
             return _NAN
         if low.endswith("j") or "_" in s:
+            return _NAN
+        if _JS_DECIMAL.match(s) is None:
+            # float() also takes inner whitespace controls and
+            # non-ASCII digits; StrDecimalLiteral does not
             return _NAN
         try:
             return float(s)

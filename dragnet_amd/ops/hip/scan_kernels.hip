@@ -17,6 +17,7 @@
 
 #include "common.h"
 #include <hip/hip_runtime.h>
+#include "dec2dbl.h"
 
 namespace dn {
 
@@ -427,20 +428,20 @@ struct FV {
 // -------------------------------------------------------------------
 // JSON number parsing (strict JSON grammar; value as double)
 
-// v * 10^ex without libm pow (exact for |ex| <= 22 when v < 2^53)
-DEV double scale10(double v, long ex) {
-  if (ex > 350) return v * __builtin_inf();
-  if (ex < -350) return v * 0.0;
-  while (ex > 22) { v *= 1e22; ex -= 22; }
-  while (ex < -22) { v /= 1e22; ex += 22; }
-  return ex >= 0 ? v * P10_TBL[ex] : v / P10_TBL[-ex];
+// mant * 10^ex, correctly rounded (dec2dbl.h: exact one-rounding fast
+// path, Eisel-Lemire out of line behind it).  Shared by the JSON
+// number parser and js_to_number.
+DEV double scale10(uint64_t mant, long ex) {
+  return dn_dec2dbl(mant, ex, P10_TBL);
 }
 
 struct NumOut { double v; bool ok; };
 
 // SWAR digit-run scan: consume the run of ASCII digits at c.pos,
 // folding into mant (10^ndig positional, capped at 19 significant
-// digits with the overflow counted in extra).  Returns the number of
+// digits with the overflow counted in extra).  Leading zeros (mant
+// still 0) are not significant: they leave ndig alone, so the cap
+// never eats real digits of 0.000...0123.  Returns the number of
 // digits consumed.  The classifier flags the FIRST non-digit exactly
 // (carries out of a non-digit byte only corrupt LATER bytes, which
 // are beyond the stop point by construction).
@@ -458,7 +459,7 @@ DEV int scan_digit_run(CursorT<BS>& c, uint64_t& mant, int& ndig,
     uint32_t avail = c.end - c.pos;
     if (n > avail) n = avail;
     if (n == 0) break;
-    if (n == 8 && ndig + 8 <= 19) {
+    if (n == 8 && mant != 0 && ndig + 8 <= 19) {
       // 3-multiply 8-digit fold (first digit in the LOW byte = most
       // significant)
       uint64_t pairs = (t * ((10ull << 8) + 1)) >> 8;
@@ -471,8 +472,10 @@ DEV int scan_digit_run(CursorT<BS>& c, uint64_t& mant, int& ndig,
     } else {
       for (uint32_t k = 0; k < n; k++) {
         uint32_t d = (uint32_t)(w >> (8 * k)) & 0xFF;
-        if (ndig < 19) { mant = mant * 10u + (d - '0'); ndig++; }
-        else extra++;
+        if (ndig < 19) {
+          mant = mant * 10u + (d - '0');
+          ndig += (mant != 0);
+        } else extra++;
       }
     }
     c.pos += n;
@@ -493,7 +496,7 @@ DEV NumOut parse_json_number(CursorT<BS>& c) {
   int ndig = 0, extra_exp = 0;
   uint8_t b = c.peek();
   if (b == '0') {
-    c.pos++; ndig = 1;
+    c.pos++;
     if (!c.eof()) { uint8_t nb = c.peek(); if (nb >= '0' && nb <= '9') return out; }
   } else if (b >= '1' && b <= '9') {
     scan_digit_run(c, mant, ndig, extra_exp);
@@ -504,10 +507,10 @@ DEV NumOut parse_json_number(CursorT<BS>& c) {
   if (!c.eof() && c.peek() == '.') {
     c.pos++;
     int fdig = 0, fex = 0;
-    int nd0 = ndig;
     fdig = scan_digit_run(c, mant, ndig, fex);
-    extra_exp -= (ndig - nd0);  // significant fraction digits
-    (void)fex;  // truncated fraction digits shift nothing
+    // every fraction digit folded into mant shifts the exponent
+    // (leading zeros included); truncated ones shift nothing
+    extra_exp -= (fdig - fex);
     if (fdig == 0) return out;
   }
   // exponent
@@ -529,10 +532,94 @@ DEV NumOut parse_json_number(CursorT<BS>& c) {
     if (edig == 0) return out;
   }
   long exp10 = esign * e10 + extra_exp;
-  double v = scale10((double)mant, exp10);
+  double v = scale10(mant, exp10);
   out.v = neg ? -v : v;
   out.ok = true;
   return out;
+}
+
+// Whitespace trim of a RAW (still JSON-escaped) string span, matching
+// what the oracle trims after unescaping.  Raw bytes cover the plain
+// space; every other ASCII whitespace can only appear in a JSON string
+// as an escape (\t \n \r \f or \u00XX), which the cold helper below
+// peels off both ends.  py_ws selects Python str.strip()'s ASCII set
+// (U+001C..U+001F and U+0085, no U+FEFF: jsdate.parse_ms) over JS
+// trim's (krill.to_number).  Non-ASCII whitespace spelled as raw
+// UTF-8 bytes is not trimmed (COMPONENTS.md).
+DEV bool raw_ws(uint8_t b) {
+  return b == ' ' || b == '\t' || b == '\r' || b == '\n' || b == '\f' ||
+         b == '\v';
+}
+
+// length (2 or 6) of a whitespace escape starting at off+p, else 0
+template <class BS>
+DEV uint32_t ws_escape_at(BS BV, uint32_t off, uint32_t p, uint32_t j,
+                          bool py_ws) {
+  if (p + 2 > j || BV.at(off + p) != '\\') return 0;
+  uint8_t e = BV.at(off + p + 1);
+  if (e == 't' || e == 'n' || e == 'r' || e == 'f') return 2;
+  if (e != 'u' || p + 6 > j) return 0;
+  uint32_t cp = 0;
+  for (int k = 2; k < 6; k++) {
+    uint8_t x = BV.at(off + p + k);
+    uint32_t d;
+    if (x >= '0' && x <= '9') d = x - '0';
+    else if (x >= 'a' && x <= 'f') d = x - 'a' + 10;
+    else if (x >= 'A' && x <= 'F') d = x - 'A' + 10;
+    else return 0;
+    cp = cp * 16 + d;
+  }
+  bool ws = (cp >= 0x09 && cp <= 0x0D) || cp == 0x20 || cp == 0xA0 ||
+            cp == 0x1680 || (cp >= 0x2000 && cp <= 0x200A) ||
+            cp == 0x2028 || cp == 0x2029 || cp == 0x202F ||
+            cp == 0x205F || cp == 0x3000 ||
+            (py_ws ? ((cp >= 0x1C && cp <= 0x1F) || cp == 0x85)
+                   : cp == 0xFEFF);
+  return ws ? 6u : 0u;
+}
+
+// (inlined, values in and packed i | j << 32 out: measured, an
+// out-of-line copy costs every scan kernel 8+ bytes of scratch for
+// its callee-saved registers, and reference parameters 24 more)
+template <class BS>
+DEV uint64_t trim_escaped_ws(BS BV, uint32_t off, uint32_t i, uint32_t j,
+                         bool py_ws) {
+  while (i < j) {
+    if (raw_ws(BV.at(off + i))) { i++; continue; }
+    uint32_t n = ws_escape_at(BV, off, i, j, py_ws);
+    if (n == 0) break;
+    i += n;
+  }
+  while (j > i) {
+    if (raw_ws(BV.at(off + j - 1))) { j--; continue; }
+    uint32_t n = 0;
+    if (j - i >= 2 && ws_escape_at(BV, off, j - 2, j, py_ws) == 2) n = 2;
+    else if (j - i >= 6 && ws_escape_at(BV, off, j - 6, j, py_ws) == 6) n = 6;
+    if (n == 0) break;
+    // the backslash starts an escape only if an even number of
+    // backslashes precede it (else it is the tail of an escaped "\\")
+    uint32_t run = 0;
+    for (uint32_t k = j - n; k > i && BV.at(off + k - 1) == '\\'; k--) run++;
+    if (run & 1) break;
+    j -= n;
+  }
+  return (uint64_t)i | ((uint64_t)j << 32);
+}
+
+// trim [i, j) of the span at off: raw bytes first, escapes only when a
+// backslash sits where an end-of-span escape would start
+template <class BS>
+DEV void trim_ws(BS BV, uint32_t off, uint32_t& i, uint32_t& j, bool py_ws) {
+  while (i < j && raw_ws(BV.at(off + i))) i++;
+  while (j > i && raw_ws(BV.at(off + j - 1))) j--;
+  if (j - i >= 2 &&
+      (BV.at(off + i) == '\\' || BV.at(off + j - 2) == '\\' ||
+       (j - i >= 6 && BV.at(off + j - 6) == '\\')))
+  {
+    uint64_t ij = trim_escaped_ws(BV, off, i, j, py_ws);
+    i = (uint32_t)ij;
+    j = (uint32_t)(ij >> 32);
+  }
 }
 
 // JavaScript ToNumber for record strings (mirrors krill.to_number):
@@ -540,8 +627,7 @@ DEV NumOut parse_json_number(CursorT<BS>& c) {
 template <class BS>
 DEV double js_to_number(BS BV, uint32_t off, uint32_t len) {
   uint32_t i = 0, j = len;
-  while (i < j) { uint8_t b = BV.at(off + i); if (b==' '||b=='\t'||b=='\r'||b=='\n'||b=='\f'||b=='\v') i++; else break; }
-  while (j > i) { uint8_t b = BV.at(off + j - 1); if (b==' '||b=='\t'||b=='\r'||b=='\n'||b=='\f'||b=='\v') j--; else break; }
+  trim_ws(BV, off, i, j, false);
   if (i == j) return 0.0;
   const double NAN_ = __builtin_nan("");
   uint32_t p = i;
@@ -561,7 +647,9 @@ DEV double js_to_number(BS BV, uint32_t off, uint32_t len) {
   if (j - p > 2 && BV.at(off+p) == '0' &&
       (BV.at(off+p+1) == 'x' || BV.at(off+p+1) == 'X')) {
     if (p != i) return NAN_;
-    uint64_t v = 0;
+    // accumulate 64 bits exactly; further digits only widen the value
+    // (sticky bit keeps the rounding of the top 64 bits honest)
+    uint64_t v = 0; int shift4 = 0; bool sticky = false;
     for (uint32_t k = p + 2; k < j; k++) {
       uint8_t b = BV.at(off+k);
       uint32_t d;
@@ -569,22 +657,25 @@ DEV double js_to_number(BS BV, uint32_t off, uint32_t len) {
       else if (b >= 'a' && b <= 'f') d = b - 'a' + 10;
       else if (b >= 'A' && b <= 'F') d = b - 'A' + 10;
       else return NAN_;
-      v = v * 16u + d;
+      if (v >> 60) { shift4++; sticky |= (d != 0); }
+      else v = v * 16u + d;
     }
+    if (sticky) v |= 1;  // v >= 2^60 here: bit 0 is below the round bit
     double r = (double)v;
-    return neg ? -r : r;
+    for (; shift4 > 0 && r < __builtin_inf(); shift4--) r *= 16.0;
+    return r;
   }
   // decimal (JS grammar: digits [. digits] [e[+-]digits], '.5' and '5.' OK)
   uint64_t mant = 0; int ndig = 0, extra = 0; bool any = false;
   while (p < j && BV.at(off+p) >= '0' && BV.at(off+p) <= '9') {
-    if (ndig < 19) { mant = mant * 10 + (BV.at(off+p)-'0'); ndig++; }
+    if (ndig < 19) { mant = mant * 10 + (BV.at(off+p)-'0'); ndig += (mant != 0); }
     else extra++;
     p++; any = true;
   }
   if (p < j && BV.at(off+p) == '.') {
     p++;
     while (p < j && BV.at(off+p) >= '0' && BV.at(off+p) <= '9') {
-      if (ndig < 19) { mant = mant * 10 + (BV.at(off+p)-'0'); ndig++; extra--; }
+      if (ndig < 19) { mant = mant * 10 + (BV.at(off+p)-'0'); ndig += (mant != 0); extra--; }
       p++; any = true;
     }
   }
@@ -604,8 +695,33 @@ DEV double js_to_number(BS BV, uint32_t off, uint32_t len) {
   }
   if (p != j) return NAN_;
   long ex = es * e10 + extra;
-  double v = scale10((double)mant, ex);
+  double v = scale10(mant, ex);
   return neg ? -v : v;
+}
+
+// -------------------------------------------------------------------
+// bucket ordinals (K4), shared by the scan and columnar kernels.  The
+// ordinal stays a DOUBLE: floor(v/step) of 1e300 is far outside any
+// integer type, and the oracle's int(floor(v/step)) is exactly that
+// double.  Ordinals inside +-ORD_BIAS pack into the key code; the rest
+// are interned as numbers (the host decodes both the same way).
+
+DEV bool finite_num(double v) {
+  return __builtin_fabs(v) < __builtin_inf();  // false for NaN too
+}
+
+DEV double bucket_ordinal(int kind, double num, double step) {
+  if (kind == BUCKET_P2) {
+    if (!(num >= 1.0)) return 0.0;
+    // floor(log2(v)) + 1 via exponent field
+    uint64_t bits = __double_as_longlong(num);
+    return (double)((int)((bits >> 52) & 0x7FF) - 1023 + 1);
+  }
+  return __builtin_floor(num / step);
+}
+
+DEV bool ord_is_small(double ordf) {
+  return ordf >= -(double)ORD_BIAS && ordf < (double)ORD_BIAS;
 }
 
 // -------------------------------------------------------------------
@@ -631,8 +747,7 @@ DEV DateOut parse_iso_ms(BS BV, uint32_t off, uint32_t len) {
   DateOut out; out.ok = false; out.ms = 0;
   // trim
   uint32_t i = 0, j = len;
-  while (i < j && (BV.at(off+i)==' '||BV.at(off+i)=='\t'||BV.at(off+i)=='\r'||BV.at(off+i)=='\n')) i++;
-  while (j > i && (BV.at(off+j-1)==' '||BV.at(off+j-1)=='\t'||BV.at(off+j-1)=='\r'||BV.at(off+j-1)=='\n')) j--;
+  trim_ws(BV, off, i, j, true);
   uint32_t p = i;
   auto digits = [&](int n, long& v) -> bool {
     v = 0;
@@ -1673,22 +1788,12 @@ __global__ void columnar_query_kernel(ColArgs A) {
             }
             t = T_NUM;
           }
-          if (t != T_NUM) { drop = true; break; }
-          long long ord;
-          if (B[2] == BUCKET_P2) {
-            if (!(num >= 1.0)) ord = 0;
-            else {
-              uint64_t bits = __double_as_longlong(num);
-              ord = (long long)((bits >> 52) & 0x7FF) - 1023 + 1;
-            }
+          if (t != T_NUM || !finite_num(num)) { drop = true; break; }
+          double ordf = bucket_ordinal(B[2], num, step);
+          if (ord_is_small(ordf)) {
+            code = make_code(TAG_ORD, (uint32_t)((int)ordf + ORD_BIAS));
           } else {
-            ord = (long long)__builtin_floor(num / step);
-          }
-          if (ord >= -(long long)ORD_BIAS &&
-              ord < (long long)ORD_BIAS) {
-            code = make_code(TAG_ORD, (uint32_t)(ord + ORD_BIAS));
-          } else {
-            uint32_t id = intern_number(A.ndict, (double)ord);
+            uint32_t id = intern_number(A.ndict, ordf);
             if (id == 0xFFFFFFFFu) { overflow = true; break; }
             code = make_code(TAG_NUM, id);
           }
@@ -1983,22 +2088,14 @@ DEV void process_record(BS BV, uint32_t start, uint32_t end,
               }
               t = T_NUM;
             }
-            if (t != T_NUM) { drop = true; break; }  // nonnumeric
-            long long ord;
-            if (B[2] == BUCKET_P2) {
-              if (!(num >= 1.0)) ord = 0;
-              else {
-                // floor(log2(v)) + 1 via exponent field
-                uint64_t bits = __double_as_longlong(num);
-                ord = (long long)((bits >> 52) & 0x7FF) - 1023 + 1;
-              }
+            // nonnumeric; an over-range literal (1e400) is +-Infinity
+            // and drops like the Infinity strings above
+            if (t != T_NUM || !finite_num(num)) { drop = true; break; }
+            double ordf = bucket_ordinal(B[2], num, step);
+            if (ord_is_small(ordf)) {
+              code = make_code(TAG_ORD, (uint32_t)((int)ordf + ORD_BIAS));
             } else {
-              ord = (long long)__builtin_floor(num / step);
-            }
-            if (ord >= -(long long)ORD_BIAS && ord < (long long)ORD_BIAS) {
-              code = make_code(TAG_ORD, (uint32_t)(ord + ORD_BIAS));
-            } else {
-              uint32_t id = intern_number(A.ndict, (double)ord);
+              uint32_t id = intern_number(A.ndict, ordf);
               if (id == 0xFFFFFFFFu) { overflow = true; break; }
               code = make_code(TAG_NUM, id);
             }

@@ -26,21 +26,53 @@ _INF = float("inf")
 
 
 def js_num_str(v):
-    """JavaScript String(number) for the values we encounter."""
+    """JavaScript String(number): ECMAScript Number::toString(10).
+
+    Shortest round-trip digits (Python's repr yields the same digit
+    string), laid out by the JS rules: fixed notation for
+    1e-6 <= |x| < 1e21, otherwise d[.ddd]e+N / e-N with no zero
+    padding of the exponent.  Integers arrive as Python ints (exact
+    below 2^53; the JSON parser rounds larger ones to binary64 first)
+    and go through the same path, so 1e21 prints as "1e+21"."""
     if isinstance(v, bool):
         return "true" if v else "false"
     if isinstance(v, int):
-        return str(v)
+        if -(2 ** 53) <= v <= 2 ** 53:
+            return str(v)
+        try:
+            v = float(v)
+        except OverflowError:
+            return "Infinity" if v > 0 else "-Infinity"
     if isinstance(v, float):
         if v != v:
             return "NaN"
-        if v == float("inf"):
+        if v == _INF:
             return "Infinity"
-        if v == float("-inf"):
+        if v == -_INF:
             return "-Infinity"
-        if v == int(v) and abs(v) < 2 ** 53:
-            return str(int(v))
-        return repr(v)
+        if v == 0:
+            return "0"  # -0 prints as "0" too
+        sign = "-" if v < 0 else ""
+        # repr gives the shortest digits; n places the decimal point:
+        # |v| = 0.DIGITS * 10^n
+        mant, _, exp = repr(abs(v)).partition("e")
+        ip, _, fp = mant.partition(".")
+        alld = ip + fp
+        stripped = alld.lstrip("0")
+        n = len(ip) - (len(alld) - len(stripped)) + (int(exp) if exp else 0)
+        digits = stripped.rstrip("0")
+        k = len(digits)
+        if k <= n <= 21:
+            return sign + digits + "0" * (n - k)
+        if 0 < n <= 21:
+            return sign + digits[:n] + "." + digits[n:]
+        if -6 < n <= 0:
+            return sign + "0." + "0" * (-n) + digits
+        e = n - 1
+        es = ("+" if e >= 0 else "-") + str(abs(e))
+        if k == 1:
+            return sign + digits + "e" + es
+        return sign + digits[0] + "." + digits[1:] + "e" + es
     return str(v)
 
 

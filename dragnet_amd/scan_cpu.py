@@ -26,9 +26,27 @@ def _reject_const(x):
     raise ValueError("invalid JSON constant: %s" % x)
 
 
+_EXACT_INT = 2 ** 53
+
+
+def _parse_int(s):
+    """JSON.parse has only binary64: an integer literal beyond 2^53
+    rounds to the nearest double (9007199254740993 -> ...992) and an
+    over-range one becomes Infinity.  Smaller integers stay Python
+    ints (exact, and the common case)."""
+    if len(s) < 16:
+        return int(s)
+    v = int(s)
+    if -_EXACT_INT <= v <= _EXACT_INT:
+        return v
+    return float(s)  # correctly rounded; inf past the double range
+
+
 def parse_json_line(line):
-    """JSON.parse semantics: no NaN/Infinity literals."""
-    return json.loads(line, parse_constant=_reject_const)
+    """JSON.parse semantics: no NaN/Infinity literals, numbers are
+    binary64."""
+    return json.loads(line, parse_constant=_reject_const,
+                      parse_int=_parse_int)
 
 
 class FilterStage(object):

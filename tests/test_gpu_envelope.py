@@ -121,6 +121,41 @@ def test_huge_digit_numbers_conserve(engines, tmp_path):
     assert vals == cvals  # same grouping structure (2,1,1)
 
 
+def test_raw_utf8_whitespace_is_a_nonnumeric_drop(engines, tmp_path):
+    """ToNumber trims whitespace in every ESCAPED spelling, but
+    non-ASCII whitespace written as raw UTF-8 bytes (U+00A0, U+FEFF,
+    U+2003) is not trimmed on the device: the documented behavior is
+    NaN -> a nonnumeric drop under a bucketizer and a baddate drop as
+    a date (the oracle trims and accepts) — never a wrong bucket."""
+    cpu, gpu = engines
+    lines = [
+        '{"s": "\u00a012"}'.encode("utf-8"),    # raw C2 A0
+        '{"s": "12\ufeff"}'.encode("utf-8"),    # raw EF BB BF
+        b'{"s": "\\u00a012"}',                 # escaped: trimmed
+        b'{"s": "12"}',
+    ]
+    assert b"\xc2\xa0" in lines[0] and b"\xef\xbb\xbf" in lines[1]
+    query = q(breakdown_specs="s[aggr=lquantize,step=1]")
+    g = gpu_scan(gpu, tmp_path, lines, query)
+    assert stage(g, "json parser")["invalid json"] == 0
+    assert g.aggregators[0].ndropped_nonnumeric == 2
+    assert g.aggregators[0].points() == [
+        {"fields": {"s": 12}, "value": 2}]
+    # the oracle trims all four
+    f2 = tmp_path / "cpu.log"
+    f2.write_bytes(b"".join(ln + b"\n" for ln in lines))
+    c = cpu.scan([str(f2)], [query])
+    assert c.aggregators[0].points() == [
+        {"fields": {"s": 12}, "value": 4}]
+    # as a date: baddate drop
+    dl = ['{"t": "\u00a02014-05-01"}'.encode("utf-8"),
+          b'{"t": "\\u00a02014-05-01"}', b'{"t": "2014-05-01"}']
+    dq = q(breakdown_specs="ts[date,field=t,aggr=lquantize,step=86400]")
+    g = gpu_scan(gpu, tmp_path, dl, dq)
+    assert stage(g, "Datetime parser")["baddate"] == 1
+    assert total_value(g) == 2
+
+
 def test_envelope_crossing_fuzz_classification(engines, tmp_path):
     """Fuzz ACROSS the envelope (deep nesting, >19-digit numbers,
     escaped keys, binary garbage): only drop-vs-accept classification

@@ -2,8 +2,11 @@
 Differential fuzzing: random JSON records + random queries, GPU kernel
 vs CPU oracle (pytest -m gpu).
 
-Stays inside the documented parity envelope: numbers <= 15
-significant digits, ASCII keys, nesting within the validated depth.
+Stays inside the documented parity envelope: numbers <= 19
+significant digits (the device parse is correctly rounded there: 17-
+digit shortest-repr floats, exponents across the double range and
+leading-zero fractions are all generated), ASCII keys, nesting within
+the validated depth.
 Everything else is fair game: missing fields, nulls, type mixes,
 malformed/truncated lines, empty lines, duplicate keys, literal
 dotted keys (companion slots), unicode values in BOTH canonical and
@@ -12,6 +15,7 @@ backslash-u-escaped spellings (incl. surrogate pairs), deep nesting.
 
 import json
 import random
+import re
 
 import pytest
 
@@ -37,10 +41,22 @@ def rand_value(rng, depth):
         return rng.choice(STRINGS)
     if r < 0.55:
         return rng.randrange(-10000, 10000)
-    if r < 0.70:
+    if r < 0.60:
         return round(rng.uniform(-1e6, 1e6), 6)
+    if r < 0.64:
+        return rng.uniform(-1e6, 1e6)  # dumps as its 16-17 digit repr
+    if r < 0.67:
+        return rng.uniform(0, 1)
+    if r < 0.70:  # exponents across the double range
+        return rng.uniform(-10, 10) * 10.0 ** rng.randrange(-320, 308)
+    if r < 0.73:  # spelled 0.000...0ddd: raw text, see rand_line
+        return "@N%s0.%s%d@" % (rng.choice(["", "-"]),
+                                "0" * rng.randrange(1, 26),
+                                rng.randrange(1, 10 ** rng.randrange(1, 16)))
     if r < 0.78:
-        return rng.choice([1e-30, 2.5e3, 0.125, 1e15, -0.0])
+        return rng.choice([1e-30, 2.5e3, 0.125, 1e15, -0.0, 1e21, 1e-7,
+                           9007199254740993, 2 ** 63, 1.7976931348623157e308,
+                           5e-324, 123456789012345680000])
     if r < 0.86:
         return rng.choice([True, False])
     if r < 0.94:
@@ -56,20 +72,27 @@ def rand_record(rng):
     return rec
 
 
+_RAW_NUM = re.compile(r'"@N([-0-9.]+)@"')
+
+
+def dumps(val, **kw):
+    """json.dumps, with "@N<digits>@" placeholders turned into raw
+    number literals (spellings json.dumps itself never emits)."""
+    return _RAW_NUM.sub(r"\1", json.dumps(val, **kw)).encode()
+
+
 def rand_line(rng):
     r = rng.random()
     if r < 0.55:
-        return json.dumps(rec_or_scalar(rng),
-                          ensure_ascii=False).encode()
+        return dumps(rec_or_scalar(rng), ensure_ascii=False)
     if r < 0.85:
         # backslash-u-escaped spelling of the same values (keys stay
         # ASCII; escaped keys are the remaining documented divergence)
-        return json.dumps(rec_or_scalar(rng),
-                          ensure_ascii=True).encode()
+        return dumps(rec_or_scalar(rng), ensure_ascii=True)
     if r < 0.90:
         return b""  # empty line
     if r < 0.95:
-        good = json.dumps(rand_record(rng)).encode()
+        good = dumps(rand_record(rng))
         return good[:rng.randrange(len(good))]  # truncated
     return bytes(rng.randrange(33, 126)
                  for _ in range(rng.randrange(1, 30)))  # garbage
