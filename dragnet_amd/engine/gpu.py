@@ -162,7 +162,7 @@ class GpuEngine(object):
         by_name = {p["name"]: i for i, p in enumerate(params)}
         nf = len(cplan.field_sigs)
         slot_kinds = [0] * nf
-        keep = []  # device tensors referenced by the descriptor array
+        keep = []  # column tensors the descriptor array points into
         nums, soffs, slens = ([torch.empty(0)] * nf for _ in range(3))
         blobs = []
         bias = 0
@@ -207,19 +207,7 @@ class GpuEngine(object):
         for attempt in range(2):
             ctx = _ScanContext(self, cplan, agg_slots, dict_slots,
                                dict_cap, dense=False)
-            self.ops.columnar_query(
-                descs, blob_t, vals_t, nrows,
-                ctx.field_sigs, ctx.comp_slot, cplan.nf_match,
-                ctx.prog_nodes, ctx.prog_bounds,
-                ctx.const_meta, ctx.const_dvals, ctx.const_bytes,
-                ctx.metric_rows, ctx.synth_req,
-                ctx.bd_rows, ctx.bd_steps,
-                ctx.table_descs,
-                ctx.sd["state"], ctx.sd["hash"], ctx.sd["id"],
-                ctx.sd["off"], ctx.sd["len"], ctx.sd["data"],
-                ctx.sd["used"], ctx.sd["next"],
-                ctx.nd["state"], ctx.nd["bits"], ctx.nd["id"],
-                ctx.nd["next"], ctx.counters)
+            ctx.state.columnar_query(descs, blob_t, vals_t, nrows, keep)
             aggs, _stages = ctx.finalize([query])
             if not ctx.overflowed():
                 return aggs[0]
@@ -263,44 +251,45 @@ class _ScanContext(object):
             return torch.from_numpy(
                 np.ascontiguousarray(np_arr.astype(np.float64))).to(dev)
 
-        # plan buffers
-        self.field_sigs = torch.from_numpy(
-            cplan.field_sigs.view(np.int64)).to(dev)
-        self.comp_slot = torch.from_numpy(cplan.comp_slot).to(dev)
+        # plan buffers and scalars, by name
         progs, bounds = cplan.programs
-        self.prog_nodes = dev_i32(progs)
-        self.prog_bounds = dev_i32(bounds)
-        self.const_meta = dev_i32(cplan.const_meta)
-        self.const_dvals = dev_f64(cplan.const_dvals)
-        self.const_bytes = torch.from_numpy(
-            np.ascontiguousarray(cplan.const_bytes)).to(dev)
-        self.synth_slots = dev_i32(cplan.synthetic)
         metrics, sreq = cplan.metrics
-        self.metric_rows = dev_i32(metrics)
-        self.synth_req = dev_i32(sreq)
         bds, steps = cplan.breakdown_descs
-        self.bd_rows = dev_i32(bds)
-        self.bd_steps = dev_f64(steps)
-        self.nm = metrics.shape[0]
+        plan = dict(
+            field_sigs=torch.from_numpy(
+                cplan.field_sigs.view(np.int64)).to(dev),
+            comp_slot=torch.from_numpy(cplan.comp_slot).to(dev),
+            nf_match=cplan.nf_match,
+            sig_bloom=cplan.sig_bloom,
+            fields_parent_sig=cplan.fields_parent_sig,
+            prog_nodes=dev_i32(progs),
+            prog_bounds=dev_i32(bounds),
+            const_meta=dev_i32(cplan.const_meta),
+            const_dvals=dev_f64(cplan.const_dvals),
+            const_bytes=torch.from_numpy(
+                np.ascontiguousarray(cplan.const_bytes)).to(dev),
+            synth_slots=dev_i32(cplan.synthetic),
+            n_synth=cplan.n_synth,
+            metric_rows=dev_i32(metrics),
+            synth_req=dev_i32(sreq),
+            bd_rows=dev_i32(bds),
+            bd_steps=dev_f64(steps),
+            value_slot=cplan.value_slot,
+            fields_slot=cplan.fields_slot,
+            skinner=cplan.data_format == "json-skinner",
+        )
+        nm = metrics.shape[0]
 
-        # tables
-        self.tables = []
-        self.partials = []
-        for m in range(self.nm):
-            state = torch.zeros(agg_slots, **i32)
-            keys = torch.zeros(agg_slots * MAX_KEY, **i32)
-            count = torch.zeros(agg_slots, **f64)
-            self.tables.append((state, keys, count))
-            if dense:
-                self.partials.append(
-                    torch.zeros((PROWS, agg_slots), **f64))
-        descs = eng.ops.agg_descs_host(
-            [t[0] for t in self.tables], [t[1] for t in self.tables],
-            [t[2] for t in self.tables], self.partials)
-        self.table_descs = descs.to(dev)
+        # per-metric tables (+ dense partial matrices)
+        states = [torch.zeros(agg_slots, **i32) for _ in range(nm)]
+        keys = [torch.zeros(agg_slots * MAX_KEY, **i32)
+                for _ in range(nm)]
+        counts = [torch.zeros(agg_slots, **f64) for _ in range(nm)]
+        partials = [torch.zeros((PROWS, agg_slots), **f64)
+                    for _ in range(nm)] if dense else []
 
         # dictionaries
-        self.sd = dict(
+        sdict = dict(
             state=torch.zeros(dict_slots, **i32),
             hash=torch.zeros(dict_slots, dtype=torch.int64, device=dev),
             id=torch.zeros(dict_slots, **i32),
@@ -310,14 +299,22 @@ class _ScanContext(object):
             used=torch.zeros(1, **i32),
             next=torch.zeros(1, **i32),
         )
-        self.nd = dict(
+        ndict = dict(
             state=torch.zeros(dict_slots, **i32),
             bits=torch.zeros(dict_slots, dtype=torch.int64, device=dev),
             id=torch.zeros(dict_slots, **i32),
             next=torch.zeros(1, **i32),
         )
         self.counters = torch.zeros(
-            C_GLOBAL_N + self.nm * CM_N, dtype=torch.int64, device=dev)
+            C_GLOBAL_N + nm * CM_N, dtype=torch.int64, device=dev)
+
+        # The bound extension object owns all of the above (the kernel
+        # descriptors point into these tensors) and caches the launch
+        # knobs (DRAGNET_MIN_WAVES / XGRAN / LDS_STAGE) as of now.
+        self.state = eng.ops.ScanState(
+            plan=plan, states=states, keys=keys, counts=counts,
+            partials=partials, sdict=sdict, ndict=ndict,
+            counters=self.counters)
 
         self._partial = b""
         self._pinned = None
@@ -382,7 +379,7 @@ class _ScanContext(object):
         self._copy_ev.record()
         self.eng.ops.newline_index(dev_data, 0, n, self._segs,
                                    self._pos, self._nlines)
-        self._scan_call(dev_data, 0)
+        self.state.scan(dev_data, self._pos, self._nlines, 0)
 
     def overflowed(self):
         return int(self.counters[5].item()) > 0
@@ -584,7 +581,7 @@ class _ScanContext(object):
         main.wait_event(ev)
         self.eng.ops.newline_index(dev_data, 0, n, self._segs,
                                    self._pos, self._nlines)
-        self._scan_call(dev_data, 0)
+        self.state.scan(dev_data, self._pos, self._nlines, 0)
         self._fs_done[idx].record(main)
         return ev
 
@@ -681,41 +678,12 @@ class _ScanContext(object):
                 main.wait_event(self._slice_evs[k])
                 self.eng.ops.newline_index(dev_data, s, e, self._segs,
                                            self._pos, self._nlines)
-                self._scan_call(dev_data, s)
+                self.state.scan(dev_data, self._pos, self._nlines, s)
             else:
                 pos_k, nlines_k = self._slice_pos[k]
-                self._scan_call(dev_data, s, pos_k, nlines_k)
+                self.state.scan(dev_data, pos_k, nlines_k, s)
         if h2d:
             ev_done.record(main)  # last reader of this pass's buffer
-
-    def _scan_call(self, dev_data, first_start, pos=None, nlines=None,
-                   x=None):
-        self.eng.ops.scan_chunk(
-            dev_data,
-            pos if pos is not None else self._pos,
-            nlines if nlines is not None else self._nlines,
-            first_start,
-            self.field_sigs, self.comp_slot, self.cplan.nf_match,
-            self.cplan.sig_bloom, self.cplan.fields_parent_sig,
-            self.prog_nodes, self.prog_bounds,
-            self.const_meta, self.const_dvals, self.const_bytes,
-            self.synth_slots, self.cplan.n_synth,
-            self.metric_rows, self.synth_req,
-            self.bd_rows, self.bd_steps,
-            self.cplan.value_slot, self.cplan.fields_slot,
-            self.cplan.data_format == "json-skinner",
-            _env_int("DRAGNET_LDS_STAGE", 0),
-            self.table_descs,
-            self.sd["state"], self.sd["hash"], self.sd["id"],
-            self.sd["off"], self.sd["len"], self.sd["data"],
-            self.sd["used"], self.sd["next"],
-            self.nd["state"], self.nd["bits"], self.nd["id"],
-            self.nd["next"],
-            self.counters,
-            x["xdata"] if x else dev_data,
-            x["wave_base"] if x else self.counters,
-            x["rec_len"] if x else self.counters,
-            x["n_slots"] if x else 0)
 
     # ---- wave-transposed staging (prototype; DRAGNET_XPOSE) ----
 
@@ -806,9 +774,9 @@ class _ScanContext(object):
 
     def scan_xpose(self):
         """One scan pass over the wave-transposed staging."""
-        rl = self._x["rec_len"]
-        self._scan_call(self._x["xdata"], 0, pos=rl, nlines=rl,
-                        x=self._x)
+        x = self._x
+        self.state.scan_xpose(x["xdata"], x["wave_base"], x["rec_len"],
+                              x["n_slots"])
 
     def make_graph(self, h2d=True, xpose=False):
         """Capture reset + the whole scan pass into a hipGraph so a
@@ -840,11 +808,7 @@ class _ScanContext(object):
         """Zero tables/dictionaries/counters for a fresh scan job
         (one binding call; ~10 separate .zero_() dispatches otherwise
         show up at 5 ms/step)."""
-        self.eng.ops.scan_reset(
-            [t[0] for t in self.tables], [t[2] for t in self.tables],
-            self.sd["state"], self.sd["used"], self.sd["next"],
-            self.nd["state"], self.nd["next"], self.counters,
-            self.partials)
+        self.state.reset()
 
     # ---- results ----
 
@@ -860,15 +824,7 @@ class _ScanContext(object):
         current stream before the reset's zeroing), which lets a caller
         software-pipeline host-side decode of step k with step k+1's
         copies/kernels (bench.py streaming mode)."""
-        r = self.eng.ops.extract_all(
-            [t[0] for t in self.tables], [t[1] for t in self.tables],
-            [t[2] for t in self.tables], self.agg_slots,
-            self.sd["state"], self.sd["hash"], self.sd["id"],
-            self.sd["off"], self.sd["len"], self.sd["data"],
-            self.sd["used"], self.sd["next"],
-            self.nd["state"], self.nd["bits"], self.nd["id"],
-            self.nd["next"], self.counters, self.dict_slots,
-            self.partials)
+        r = self.state.extract_all()
         h = {"cnt": r[0], "n_str": r[1], "n_num": r[2], "used": r[3],
              "blob": r[4], "str_off": r[5], "str_len": r[6],
              "numbers": r[7],
@@ -1056,40 +1012,3 @@ def _decode_json_string(raw):
         except ValueError:
             return s
     return s
-
-
-def _read_files(files, chunk_size, prefetch=4):
-    """Chunked concatenated reader with a background prefetch thread
-    (the reference reads files with concurrency 2 through catstreams,
-    lib/datasource-file.js:252-288; here a reader thread keeps the
-    GPU fed while it scans the previous chunk)."""
-    import queue
-    import threading
-
-    q = queue.Queue(maxsize=prefetch)
-    err = []
-
-    def reader():
-        try:
-            for path in files:
-                with open(path, "rb", buffering=0) as f:
-                    while True:
-                        chunk = f.read(chunk_size)
-                        if not chunk:
-                            break
-                        q.put(chunk)
-        except Exception as e:  # surfaced on the consumer side
-            err.append(e)
-        finally:
-            q.put(None)
-
-    t = threading.Thread(target=reader, daemon=True)
-    t.start()
-    while True:
-        chunk = q.get()
-        if chunk is None:
-            break
-        yield chunk
-    t.join()
-    if err:
-        raise err[0]

@@ -1535,6 +1535,202 @@ struct LdsCacheEntry {
   double count;
 };
 
+// Dynamic-LDS layout of the scan and columnar kernels:
+//   fv SoA | agg cache | counters [| synthetics | sig stack] | tile
+// Defined ONCE: the kernels carve their LDS with it and the host sizes
+// the launch (and checks the 160 KiB budget) from the same offsets.
+// parse_state adds what only the NDJSON parser needs; the columnar
+// kernel has neither synthetics nor a sig stack.
+struct LdsLayout {
+  size_t fv_soff, fv_slen, fv_type, cache, lcnt, synth, sig, tile, total;
+  __host__ __device__ __forceinline__
+  LdsLayout(int nf, int nm, int ns, bool parse_state) {
+    size_t off = 0;
+    fv_soff = off; off += (size_t)nf * BLOCK * sizeof(uint32_t);
+    fv_slen = off; off += (size_t)nf * BLOCK * sizeof(uint32_t);
+    fv_type = off; off += (size_t)nf * BLOCK * sizeof(uint8_t);
+    off = (off + 15) & ~(size_t)15;
+    cache = off; off += (size_t)LDS_CACHE * sizeof(LdsCacheEntry);
+    lcnt = off;
+    off += (size_t)(C_GLOBAL_N + nm * CM_N) * sizeof(unsigned long long);
+    synth = sig = off;
+    if (parse_state) {
+      // sized by the ACTUAL synthetic count: the flagship plan has zero
+      // synthetics and an unconditional MAX_SYNTH reservation (16 KB)
+      // was costing a whole extra block of occupancy per CU
+      off += (size_t)ns * BLOCK * sizeof(double);
+      sig = off; off += (size_t)SIG_DEPTH * BLOCK * sizeof(uint64_t);
+    }
+    off = (off + 15) & ~(size_t)15;
+    tile = off;         // optional staging tile: ScanArgs.tile_cap bytes
+    total = off + 64;   // slack
+  }
+};
+
+// -------------------------------------------------------------------
+// aggregation tail shared by the scan and columnar kernels: key-column
+// encoding, the LDS combining cache, and its block-level init / flush
+
+// Encode one breakdown column (value type t: num, or the span so/sl)
+// to its u32 key code (K4: bucketize; dict-intern).  Returns false
+// with drop set (the record is nonnumeric for a bucketized column) or
+// overflow set (a dictionary is full).
+template <class BS>
+DEV bool encode_key_col(const StrDict& sdict, const NumDict& ndict, BS BV,
+                       uint8_t t, double num, uint32_t so, uint32_t sl,
+                       int bucket, double step, uint32_t& code,
+                        bool& drop, bool& overflow) {
+  if (bucket != BUCKET_NONE) {
+    if (t == T_STR) {
+      // numeric STRINGS coerce for bucketized fields (JS arithmetic in
+      // the reference's bucketizer: its own golden counts
+      // {"latency": "26"} into the p2 histogram —
+      // tests/data/2014/05-05/more.log:1); NaN / +-Infinity drop as
+      // nonnumeric
+      num = js_to_number(BV, so, sl);
+      if (!(num == num) || num == __builtin_inf() ||
+          num == -__builtin_inf())
+        { drop = true; return false; }
+      t = T_NUM;
+    }
+    // nonnumeric; an over-range literal (1e400) is +-Infinity and
+    // drops like the Infinity strings above
+    if (t != T_NUM || !finite_num(num)) { drop = true; return false; }
+    double ordf = bucket_ordinal(bucket, num, step);
+    if (ord_is_small(ordf)) {
+      code = make_code(TAG_ORD, (uint32_t)((int)ordf + ORD_BIAS));
+    } else {
+      uint32_t id = intern_number(ndict, ordf);
+      if (id == 0xFFFFFFFFu) { overflow = true; return false; }
+      code = make_code(TAG_NUM, id);
+    }
+  } else if (t == T_MISSING) {
+    code = make_code(TAG_SPECIAL, SPECIAL_UNDEF);
+  } else if (t == T_NULL) {
+    code = make_code(TAG_SPECIAL, SPECIAL_NULL);
+  } else if (t == T_TRUE) {
+    code = make_code(TAG_SPECIAL, SPECIAL_TRUE);
+  } else if (t == T_FALSE) {
+    code = make_code(TAG_SPECIAL, SPECIAL_FALSE);
+  } else if (t == T_OBJ) {
+    code = make_code(TAG_SPECIAL, SPECIAL_OBJECT);
+  } else if (t == T_ARR) {
+    // intern the raw JSON span; the host canonicalizes it with JS
+    // Array.toString semantics (plan.decode_key)
+    uint32_t id = intern_string(sdict, BV, so, sl);
+    if (id == 0xFFFFFFFFu || id >= (1u << 27)) { overflow = true; return false; }
+    code = make_code(TAG_SPECIAL, SPECIAL_ARRJSON | (id << 3));
+  } else if (t == T_NUM) {
+    uint32_t id = intern_number(ndict, num);
+    if (id == 0xFFFFFFFFu) { overflow = true; return false; }
+    code = make_code(TAG_NUM, id);
+  } else {  // T_STR
+    uint32_t id = intern_string(sdict, BV, so, sl);
+    if (id == 0xFFFFFFFFu) { overflow = true; return false; }
+    code = make_code(TAG_STR, id);
+  }
+  return true;
+}
+
+// LDS combining cache: hash of (metric, key); never 0 (0 = empty slot)
+DEV uint64_t agg_key_hash(int m, const uint32_t* key) {
+  uint64_t kh = mix64((uint64_t)m * 0x9E3779B97F4A7C15ull + 1);
+  for (int k = 0; k < MAX_KEY; k++) kh = mix64(kh ^ key[k]);
+  return kh == 0 ? 1 : kh;
+}
+
+// Add (metric m, key, weight) to the block's LDS cache, falling through
+// to the global table when the probes are exhausted.
+//
+// NOTE on the LDS cache race: two lanes with DIFFERENT keys that
+// collide on the same 64-bit kh would mis-combine.  kh is a 64-bit mix
+// of the full key; a collision needs two distinct key tuples in one
+// block with equal mix64 chains (~2^-64 per pair) — accepted and
+// documented (SURVEY parity corners).  Identity (metric + key words)
+// is nevertheless verified for the common same-slot case; the claim
+// fill is racy only against lanes carrying the SAME kh.
+//
+// UNROLL is the probe loop's unroll count, fixed per kernel to the
+// shape each compiled to before the loop was shared: rolled (1) in the
+// scan kernels, where unrolling raises SGPR spills 226 -> 242 and
+// measured 1.3% slower device-resident; fully unrolled (8) in the
+// columnar kernel, where rolling raises them 165 -> 196.
+template <int UNROLL>
+DEV void lds_cache_add(LdsCacheEntry* cache, AggTable* tables,
+                       unsigned long long* counters,
+                       unsigned long long* lcnt, int m,
+                       const uint32_t* key, int nk, uint64_t kh,
+                       double weight) {
+  bool cached = false;
+  uint32_t ci = (uint32_t)kh & (LDS_CACHE - 1);
+  // 8 probes: a hot key that loses every probe degrades to per-record
+  // contended global inserts (measured 4x slower on low-cardinality
+  // ordinal breakdowns with 2 probes)
+#pragma unroll UNROLL
+  for (int attempt = 0; attempt < 8; attempt++) {
+    unsigned long long prev = atomicCAS(
+        (unsigned long long*)&cache[ci].hash, 0ull,
+        (unsigned long long)kh);
+    if (prev == 0) {
+      // claimed: fill identity (hash claim is the sync point;
+      // same-key lanes re-check identity below)
+      cache[ci].metric = m;
+      for (int k = 0; k < MAX_KEY; k++) cache[ci].key[k] = key[k];
+      atomicAdd(&cache[ci].count, weight);
+      cached = true;
+      break;
+    }
+    if (prev == (unsigned long long)kh && cache[ci].metric == m) {
+      bool same = true;
+      for (int k = 0; k < MAX_KEY; k++)
+        if (cache[ci].key[k] != key[k]) { same = false; break; }
+      if (same) {
+        atomicAdd(&cache[ci].count, weight);
+        cached = true;
+        break;
+      }
+    }
+    ci = (ci + 1) & (LDS_CACHE - 1);
+  }
+  if (!cached) {
+    if (!agg_add(tables[m], key, nk, weight, &counters[C_OVERFLOW]))
+      atomicAdd(&lcnt[C_OVERFLOW], 1ull);
+  }
+}
+
+// Block start: empty the cache and zero the block-local counters.
+DEV void block_agg_init(LdsCacheEntry* cache, unsigned long long* lcnt,
+                        int ncnt) {
+  for (int i = threadIdx.x; i < LDS_CACHE; i += BLOCK) {
+    cache[i].hash = 0;
+    cache[i].metric = 0;
+    for (int k = 0; k < MAX_KEY; k++) cache[i].key[k] = 0;
+    cache[i].count = 0.0;
+  }
+  for (int i = threadIdx.x; i < ncnt; i += BLOCK) lcnt[i] = 0;
+  __syncthreads();
+}
+
+// Block end: flush the cache into the global tables, then the
+// block-local counters into the global ones.
+DEV void block_agg_flush(LdsCacheEntry* cache, unsigned long long* lcnt,
+                         int ncnt, const PlanView& P, AggTable* tables,
+                         unsigned long long* counters) {
+  __syncthreads();
+  for (int i = threadIdx.x; i < LDS_CACHE; i += BLOCK) {
+    if (cache[i].hash != 0) {
+      if (!agg_add(tables[cache[i].metric], cache[i].key,
+                   P.metric_rows[cache[i].metric * 8 + 1],
+                   cache[i].count, &counters[C_OVERFLOW]))
+        atomicAdd(&lcnt[C_OVERFLOW], 1ull);
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < ncnt; i += BLOCK) {
+    if (lcnt[i]) atomicAdd(&counters[i], lcnt[i]);
+  }
+}
+
 // ---- newline indexing (device-side, no host sync) ----
 // Three passes over 2 KiB segments: count, exclusive-scan, write.
 // Positions come out globally sorted because each segment writes its
@@ -1703,36 +1899,26 @@ struct ColArgs {
   unsigned long long* counters;
 };
 
-__launch_bounds__(BLOCK, 4)
+// 5 waves/SIMD is what this kernel compiles to (91 VGPRs); holding the
+// register allocator to it keeps the SGPR spill count at the level the
+// kernel had before it shared the aggregation tail (157 vs 163; at a
+// bound of 4 the allocator lands on 165).
+__launch_bounds__(BLOCK, 5)
 __global__ void columnar_query_kernel(ColArgs A) {
   extern __shared__ __attribute__((aligned(16))) char smemc[];
   const PlanView& P = A.P;
   const int nf = P.nf;
-  size_t off = 0;
-  uint32_t* fv_soff = reinterpret_cast<uint32_t*>(smemc + off);
-  off += (size_t)nf * BLOCK * sizeof(uint32_t);
-  uint32_t* fv_slen = reinterpret_cast<uint32_t*>(smemc + off);
-  off += (size_t)nf * BLOCK * sizeof(uint32_t);
-  uint8_t* fv_type = reinterpret_cast<uint8_t*>(smemc + off);
-  off += (size_t)nf * BLOCK * sizeof(uint8_t);
-  off = (off + 15) & ~(size_t)15;
-  LdsCacheEntry* cache = reinterpret_cast<LdsCacheEntry*>(smemc + off);
-  off += (size_t)LDS_CACHE * sizeof(LdsCacheEntry);
+  const LdsLayout L(nf, P.nm, 0, false);
+  LdsCacheEntry* cache = reinterpret_cast<LdsCacheEntry*>(smemc + L.cache);
   unsigned long long* lcnt =
-      reinterpret_cast<unsigned long long*>(smemc + off);
+      reinterpret_cast<unsigned long long*>(smemc + L.lcnt);
   const int NCNT = C_GLOBAL_N + P.nm * CM_N;
-
-  for (int i = threadIdx.x; i < LDS_CACHE; i += BLOCK) {
-    cache[i].hash = 0;
-    cache[i].metric = 0;
-    for (int k = 0; k < MAX_KEY; k++) cache[i].key[k] = 0;
-    cache[i].count = 0.0;
-  }
-  for (int i = threadIdx.x; i < NCNT; i += BLOCK) lcnt[i] = 0;
-  __syncthreads();
+  block_agg_init(cache, lcnt, NCNT);
 
   FV fv;
-  fv.type = fv_type; fv.soff = fv_soff; fv.slen = fv_slen;
+  fv.type = reinterpret_cast<uint8_t*>(smemc + L.fv_type);
+  fv.soff = reinterpret_cast<uint32_t*>(smemc + L.fv_soff);
+  fv.slen = reinterpret_cast<uint32_t*>(smemc + L.fv_slen);
   fv.tid = threadIdx.x;
   Bytes BV;
   BV.mem = A.blob;
@@ -1772,42 +1958,13 @@ __global__ void columnar_query_kernel(ColArgs A) {
       bool drop = false, overflow = false;
       for (int bi = 0; bi < nk; bi++) {
         const int32_t* B = &P.bd_rows[(M[2] + bi) * 4];
-        double step = P.bd_steps[M[2] + bi];
         int slot = B[1];  // columnar plans use kind-0 refs only
-        uint8_t t = fv.get_type(slot);
-        double num = fv.get_num(slot);
-        uint32_t so = fv.get_soff(slot), sl = fv.get_slen(slot);
         uint32_t code;
-        if (B[2] != BUCKET_NONE) {
-          if (t == T_STR) {
-            num = js_to_number(BV, so, sl);
-            if (!(num == num) || num == __builtin_inf() ||
-                num == -__builtin_inf()) {
-              drop = true;
-              break;
-            }
-            t = T_NUM;
-          }
-          if (t != T_NUM || !finite_num(num)) { drop = true; break; }
-          double ordf = bucket_ordinal(B[2], num, step);
-          if (ord_is_small(ordf)) {
-            code = make_code(TAG_ORD, (uint32_t)((int)ordf + ORD_BIAS));
-          } else {
-            uint32_t id = intern_number(A.ndict, ordf);
-            if (id == 0xFFFFFFFFu) { overflow = true; break; }
-            code = make_code(TAG_NUM, id);
-          }
-        } else if (t == T_MISSING) {
-          code = make_code(TAG_SPECIAL, SPECIAL_UNDEF);
-        } else if (t == T_NUM) {
-          uint32_t id = intern_number(A.ndict, num);
-          if (id == 0xFFFFFFFFu) { overflow = true; break; }
-          code = make_code(TAG_NUM, id);
-        } else {  // T_STR
-          uint32_t id = intern_string(A.sdict, BV, so, sl);
-          if (id == 0xFFFFFFFFu) { overflow = true; break; }
-          code = make_code(TAG_STR, id);
-        }
+        if (!encode_key_col(A.sdict, A.ndict, BV, fv.get_type(slot),
+                            fv.get_num(slot), fv.get_soff(slot),
+                            fv.get_slen(slot), B[2],
+                            P.bd_steps[M[2] + bi], code, drop, overflow))
+          break;
 #pragma unroll
         for (int kk = 0; kk < MAX_KEY; kk++)
           if (kk == bi) key[kk] = code;
@@ -1818,55 +1975,12 @@ __global__ void columnar_query_kernel(ColArgs A) {
       for (int k = 0; k < MAX_KEY; k++)
         if (k >= nk) key[k] = 0;
 
-      uint64_t kh = mix64((uint64_t)m * 0x9E3779B97F4A7C15ull + 1);
-      for (int k = 0; k < MAX_KEY; k++) kh = mix64(kh ^ key[k]);
-      if (kh == 0) kh = 1;
-      bool cached = false;
-      uint32_t ci = (uint32_t)kh & (LDS_CACHE - 1);
-      for (int attempt = 0; attempt < 8; attempt++) {
-        unsigned long long prev = atomicCAS(
-            (unsigned long long*)&cache[ci].hash, 0ull,
-            (unsigned long long)kh);
-        if (prev == 0) {
-          cache[ci].metric = m;
-          for (int k = 0; k < MAX_KEY; k++) cache[ci].key[k] = key[k];
-          atomicAdd(&cache[ci].count, weight);
-          cached = true;
-          break;
-        }
-        if (prev == (unsigned long long)kh && cache[ci].metric == m) {
-          bool same = true;
-          for (int k = 0; k < MAX_KEY; k++)
-            if (cache[ci].key[k] != key[k]) { same = false; break; }
-          if (same) {
-            atomicAdd(&cache[ci].count, weight);
-            cached = true;
-            break;
-          }
-        }
-        ci = (ci + 1) & (LDS_CACHE - 1);
-      }
-      if (!cached) {
-        if (!agg_add(A.tables[m], key, nk, weight,
-                     &A.counters[C_OVERFLOW]))
-          atomicAdd(&lcnt[C_OVERFLOW], 1ull);
-      }
+      lds_cache_add<8>(cache, A.tables, A.counters, lcnt, m, key, nk,
+                    agg_key_hash(m, key), weight);
     }
   }
 
-  __syncthreads();
-  for (int i = threadIdx.x; i < LDS_CACHE; i += BLOCK) {
-    if (cache[i].hash != 0) {
-      if (!agg_add(A.tables[cache[i].metric], cache[i].key,
-                   P.metric_rows[cache[i].metric * 8 + 1],
-                   cache[i].count, &A.counters[C_OVERFLOW]))
-        atomicAdd(&lcnt[C_OVERFLOW], 1ull);
-    }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < NCNT; i += BLOCK) {
-    if (lcnt[i]) atomicAdd(&A.counters[i], lcnt[i]);
-  }
+  block_agg_flush(cache, lcnt, NCNT, P, A.tables, A.counters);
 }
 
 // Device-side wave-transpose builder: scatter each (length-sorted)
@@ -2073,59 +2187,9 @@ DEV void process_record(BS BV, uint32_t start, uint32_t end,
             so = fv.get_soff(slot); sl = fv.get_slen(slot);
           }
           uint32_t code;
-          if (B[2] != BUCKET_NONE) {
-            if (t == T_STR) {
-              // numeric STRINGS coerce for bucketized fields (JS
-              // arithmetic in the reference's bucketizer: its own
-              // golden counts {"latency": "26"} into the p2
-              // histogram — tests/data/2014/05-05/more.log:1);
-              // NaN / +-Infinity drop as nonnumeric
-              num = js_to_number(BV, so, sl);
-              if (!(num == num) || num == __builtin_inf() ||
-                  num == -__builtin_inf()) {
-                drop = true;
-                break;
-              }
-              t = T_NUM;
-            }
-            // nonnumeric; an over-range literal (1e400) is +-Infinity
-            // and drops like the Infinity strings above
-            if (t != T_NUM || !finite_num(num)) { drop = true; break; }
-            double ordf = bucket_ordinal(B[2], num, step);
-            if (ord_is_small(ordf)) {
-              code = make_code(TAG_ORD, (uint32_t)((int)ordf + ORD_BIAS));
-            } else {
-              uint32_t id = intern_number(A.ndict, ordf);
-              if (id == 0xFFFFFFFFu) { overflow = true; break; }
-              code = make_code(TAG_NUM, id);
-            }
-          } else if (t == T_MISSING) {
-            code = make_code(TAG_SPECIAL, SPECIAL_UNDEF);
-          } else if (t == T_NULL) {
-            code = make_code(TAG_SPECIAL, SPECIAL_NULL);
-          } else if (t == T_TRUE) {
-            code = make_code(TAG_SPECIAL, SPECIAL_TRUE);
-          } else if (t == T_FALSE) {
-            code = make_code(TAG_SPECIAL, SPECIAL_FALSE);
-          } else if (t == T_OBJ) {
-            code = make_code(TAG_SPECIAL, SPECIAL_OBJECT);
-          } else if (t == T_ARR) {
-            // intern the raw JSON span; the host canonicalizes it
-            // with JS Array.toString semantics (plan.decode_key)
-            uint32_t id = intern_string(A.sdict, BV, so, sl);
-            if (id == 0xFFFFFFFFu || id >= (1u << 27)) {
-              overflow = true; break;
-            }
-            code = make_code(TAG_SPECIAL, SPECIAL_ARRJSON | (id << 3));
-          } else if (t == T_NUM) {
-            uint32_t id = intern_number(A.ndict, num);
-            if (id == 0xFFFFFFFFu) { overflow = true; break; }
-            code = make_code(TAG_NUM, id);
-          } else {  // T_STR
-            uint32_t id = intern_string(A.sdict, BV, so, sl);
-            if (id == 0xFFFFFFFFu) { overflow = true; break; }
-            code = make_code(TAG_STR, id);
-          }
+          if (!encode_key_col(A.sdict, A.ndict, BV, t, num, so, sl, B[2],
+                              step, code, drop, overflow))
+            break;
           // constant-index write keeps key[] in registers
 #pragma unroll
           for (int kk = 0; kk < MAX_KEY; kk++)
@@ -2137,10 +2201,7 @@ DEV void process_record(BS BV, uint32_t start, uint32_t end,
         for (int k = 0; k < MAX_KEY; k++)
           if (k >= nk) key[k] = 0;
 
-        // LDS combining cache: hash (metric, key)
-        uint64_t kh = mix64((uint64_t)m * 0x9E3779B97F4A7C15ull + 1);
-        for (int k = 0; k < MAX_KEY; k++) kh = mix64(kh ^ key[k]);
-        if (kh == 0) kh = 1;
+        uint64_t kh = agg_key_hash(m, key);
 
         // Wave-level pre-combining: lanes carrying the same key
         // elect one leader per distinct kh which adds the whole
@@ -2165,42 +2226,8 @@ DEV void process_record(BS BV, uint32_t start, uint32_t end,
           if (!leader) continue;  // combined into the leader's add
           weight = wsum;
         }
-        bool cached = false;
-        uint32_t ci = (uint32_t)kh & (LDS_CACHE - 1);
-        // 8 probes: a hot key that loses every probe degrades to
-        // per-record contended global inserts (measured 4x slower
-        // on low-cardinality ordinal breakdowns with 2 probes)
-        for (int attempt = 0; attempt < 8; attempt++) {
-          unsigned long long prev = atomicCAS(
-              (unsigned long long*)&cache[ci].hash, 0ull,
-              (unsigned long long)kh);
-          if (prev == 0) {
-            // claimed: fill identity (hash claim is the sync point;
-            // same-key lanes re-check identity below)
-            cache[ci].metric = m;
-            for (int k = 0; k < MAX_KEY; k++) cache[ci].key[k] = key[k];
-            atomicAdd(&cache[ci].count, weight);
-            cached = true;
-            break;
-          }
-          if (prev == (unsigned long long)kh &&
-              cache[ci].metric == m) {
-            bool same = true;
-            for (int k = 0; k < MAX_KEY; k++)
-              if (cache[ci].key[k] != key[k]) { same = false; break; }
-            if (same) {
-              atomicAdd(&cache[ci].count, weight);
-              cached = true;
-              break;
-            }
-          }
-          ci = (ci + 1) & (LDS_CACHE - 1);
-        }
-        if (!cached) {
-          if (!agg_add(A.tables[m], key, nk, weight,
-                       &A.counters[C_OVERFLOW]))
-            atomicAdd(&lcnt[C_OVERFLOW], 1ull);
-        }
+        lds_cache_add<1>(cache, A.tables, A.counters, lcnt, m, key, nk, kh,
+                      weight);
       }
     }
   }
@@ -2211,42 +2238,20 @@ DEV void scan_kernel_body(char* smem, ScanArgs A) {
   const PlanView& P = A.P;
   const int nf = P.nf;
 
-  // LDS layout: fv SoA | agg cache | counters
-  size_t off = 0;
-  uint32_t* fv_soff = reinterpret_cast<uint32_t*>(smem + off);
-  off += (size_t)nf * BLOCK * sizeof(uint32_t);
-  uint32_t* fv_slen = reinterpret_cast<uint32_t*>(smem + off);
-  off += (size_t)nf * BLOCK * sizeof(uint32_t);
-  uint8_t* fv_type = reinterpret_cast<uint8_t*>(smem + off);
-  off += (size_t)nf * BLOCK * sizeof(uint8_t);
-  off = (off + 15) & ~(size_t)15;
-  LdsCacheEntry* cache = reinterpret_cast<LdsCacheEntry*>(smem + off);
-  off += (size_t)LDS_CACHE * sizeof(LdsCacheEntry);
-  unsigned long long* lcnt = reinterpret_cast<unsigned long long*>(smem + off);
+  const LdsLayout L(nf, P.nm, P.ns, true);
+  LdsCacheEntry* cache = reinterpret_cast<LdsCacheEntry*>(smem + L.cache);
+  unsigned long long* lcnt =
+      reinterpret_cast<unsigned long long*>(smem + L.lcnt);
   const int NCNT = C_GLOBAL_N + P.nm * CM_N;
-  off += (size_t)NCNT * sizeof(unsigned long long);
-  double* synth_lds = reinterpret_cast<double*>(smem + off);
-  // sized by the ACTUAL synthetic count: the flagship plan has zero
-  // synthetics and the unconditional MAX_SYNTH reservation (16 KB)
-  // was costing a whole extra block of occupancy per CU
-  off += (size_t)P.ns * BLOCK * sizeof(double);
-  uint64_t* sig_lds = reinterpret_cast<uint64_t*>(smem + off);
-  off += (size_t)SIG_DEPTH * BLOCK * sizeof(uint64_t);
-  off = (off + 15) & ~(size_t)15;
-  uint8_t* tile = reinterpret_cast<uint8_t*>(smem + off);  // staging
-
-  // init LDS
-  for (int i = threadIdx.x; i < LDS_CACHE; i += BLOCK) {
-    cache[i].hash = 0;
-    cache[i].metric = 0;
-    for (int k = 0; k < MAX_KEY; k++) cache[i].key[k] = 0;
-    cache[i].count = 0.0;
-  }
-  for (int i = threadIdx.x; i < NCNT; i += BLOCK) lcnt[i] = 0;
-  __syncthreads();
+  double* synth_lds = reinterpret_cast<double*>(smem + L.synth);
+  uint64_t* sig_lds = reinterpret_cast<uint64_t*>(smem + L.sig);
+  uint8_t* tile = reinterpret_cast<uint8_t*>(smem + L.tile);  // staging
+  block_agg_init(cache, lcnt, NCNT);
 
   FV fv;
-  fv.type = fv_type; fv.soff = fv_soff; fv.slen = fv_slen;
+  fv.type = reinterpret_cast<uint8_t*>(smem + L.fv_type);
+  fv.soff = reinterpret_cast<uint32_t*>(smem + L.fv_soff);
+  fv.slen = reinterpret_cast<uint32_t*>(smem + L.fv_slen);
   fv.tid = threadIdx.x;
 
   if constexpr (XP != 0) {
@@ -2315,29 +2320,8 @@ DEV void scan_kernel_body(char* smem, ScanArgs A) {
   }
   }  // XP
 
-  // flush LDS cache + counters
-  __syncthreads();
-  for (int i = threadIdx.x; i < LDS_CACHE; i += BLOCK) {
-    if (cache[i].hash != 0) {
-      if (!agg_add(A.tables[cache[i].metric], cache[i].key,
-                   P.metric_rows[cache[i].metric * 8 + 1],
-                   cache[i].count, &A.counters[C_OVERFLOW]))
-        atomicAdd(&lcnt[C_OVERFLOW], 1ull);
-    }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < NCNT; i += BLOCK) {
-    if (lcnt[i]) atomicAdd(&A.counters[i], lcnt[i]);
-  }
+  block_agg_flush(cache, lcnt, NCNT, P, A.tables, A.counters);
 }
-
-// NOTE on the LDS cache race above: two lanes with DIFFERENT keys that
-// collide on the same 64-bit kh would mis-combine.  kh is a 64-bit mix
-// of the full key; a collision needs two distinct key tuples in one
-// block with equal mix64 chains (~2^-64 per pair) — accepted and
-// documented (SURVEY parity corners).  Identity (metric + key words)
-// is nevertheless verified for the common same-slot case; the claim
-// fill is racy only against lanes carrying the SAME kh.
 
 // -------------------------------------------------------------------
 // extraction kernels

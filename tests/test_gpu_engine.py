@@ -581,3 +581,72 @@ def test_dense_slots_knob(engines, tmp_path):
         finally:
             os.environ.pop("DRAGNET_DENSE_SLOTS", None)
         assert_same(c, g)
+
+
+def _holds_tensor(val):
+    import torch
+    if isinstance(val, torch.Tensor):
+        return True
+    if isinstance(val, dict):
+        val = list(val.values())
+    return isinstance(val, (list, tuple)) and \
+        any(_holds_tensor(v) for v in val)
+
+
+def test_contexts_isolated_and_self_owned(engines, tmp_path):
+    """Two scan contexts on one engine, different plans, fed
+    interleaved: state is per context.  The bound extension object
+    owns the plan/table/dictionary tensors its descriptors point at:
+    with every other Python reference to one context's gone (and the
+    allocator given the chance to hand their memory out again), both
+    results still equal the oracle exactly."""
+    import gc
+
+    import torch
+
+    cpu, gpu = engines
+    from dragnet_amd.engine import plan as planmod
+    from dragnet_amd.engine.gpu import _ScanContext
+    from dragnet_amd.query import query_load
+    from dragnet_amd.tools.mktestdata import generate_lines
+    pool = b"".join(generate_lines(300, seed=11))
+    path = tmp_path / "pool.ndjson"
+    path.write_bytes(pool)
+    qa = query_load(filter={"eq": ["req.method", "GET"]},
+                    breakdown_specs="req.method,res.statusCode")
+    qb = query_load(breakdown_specs="latency[aggr=quantize]")
+    exp_a = cpu.scan([str(path)], [qa]).aggregators[0].points()
+    exp_b = cpu.scan([str(path)], [qb]).aggregators[0].points()
+    assert exp_a and exp_b and exp_a != exp_b
+
+    a = _ScanContext(gpu, planmod.compile_plan([qa]), agg_slots=1 << 12,
+                     dict_slots=1 << 12, dict_data_cap=1 << 20,
+                     dense=True)
+    b = _ScanContext(gpu, planmod.compile_plan([qb]), agg_slots=1 << 12,
+                     dict_slots=1 << 12, dict_data_cap=1 << 20,
+                     dense=False)
+    step = len(pool) // 5 + 1  # chunk cuts fall inside records
+    for at in range(0, len(pool), step):
+        a.feed(pool[at:at + step])
+        b.feed(pool[at:at + step])
+    a.flush()
+    b.flush()
+
+    # The plan/table/dictionary tensors were locals of a's constructor:
+    # Python holds none of them any more (counters is interface, the
+    # scan buffers are private), so only the bound state keeps them
+    # alive.  Freed memory would be handed to the junk tensors below.
+    assert not [name for name, val in vars(a).items()
+                if not name.startswith("_") and name != "counters"
+                and _holds_tensor(val)]
+    gc.collect()
+    for n in (1 << 12, 1 << 14, 1 << 16, 1 << 20, 1 << 24):
+        junk = torch.full((n,), 0x5A, dtype=torch.uint8,
+                          device=gpu.device)
+        del junk
+
+    aggs_a, _ = a.finalize([qa])
+    aggs_b, _ = b.finalize([qb])
+    assert not a.overflowed() and not b.overflowed()
+    assert aggs_a[0].points() == exp_a
+    assert aggs_b[0].points() == exp_b

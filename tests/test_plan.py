@@ -37,6 +37,24 @@ def test_constants_match_header():
     assert cval("MAX_FIELDS") == plan.MAX_FIELDS
 
 
+def test_lds_layout_pinned():
+    """The kernels' dynamic-LDS size is byte-for-byte fixed (occupancy
+    depends on it).  With a16 = round up to 16 and a 56-byte cache
+    entry:
+      scan:     a16(nf*256*9) + 128*56 + (8 + 8*nm)*8 + ns*256*8
+                + 6*256*8 + 64
+      columnar: a16(nf*256*9) + 128*56 + (8 + 8*nm)*8 + 64
+    Host-only binding: needs the built extension, not a GPU."""
+    from dragnet_amd.ops import load_ops
+    ops = load_ops(required=True)
+    # 4608 + 7168 + 128 + 0 + 12288 + 64
+    assert ops.lds_bytes(nf=2, nm=1, ns=0) == 24256
+    # 55296 + 7168 + 320 + 16384 + 12288 + 64
+    assert ops.lds_bytes(nf=24, nm=4, ns=8) == 91520
+    # 4608 + 7168 + 128 + 64
+    assert ops.lds_bytes(nf=2, nm=1, columnar=True) == 11968
+
+
 def test_program_layout():
     q = query_load(
         filter={"and": [{"eq": ["a", 1]},
