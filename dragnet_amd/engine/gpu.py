@@ -7,7 +7,8 @@ async H2D on the current HIP stream, torch-side newline indexing, one
 fused kernel launch per chunk, then table/dictionary extraction and
 host-side decode into the same canonical aggregate representation the
 CPU oracle produces (points.Aggregator) — so every downstream consumer
-(formatters, index sink, RCCL merge) is engine-agnostic.
+(formatters, index sink, RCCL merge) is engine-agnostic.  File scans
+take their chunks from the host-only framer in engine/chunks.py.
 
 Capacity handling: the hash tables and dictionaries are sized up front;
 on overflow (C_OVERFLOW counter) the whole scan is retried with 8x the
@@ -22,21 +23,17 @@ import numpy as np
 
 from ..points import Aggregator
 from . import plan as planmod
+from .chunks import _pad, choose_chunk_bytes, frame_files
 
-COUNTER_NAMES = ["lines", "invalid_json", "parsed", "ds_filtered",
-                 "ds_failedeval", "overflow"]
+# device counter slots (ops/hip/common.h CounterSlot)
+(C_LINES, C_INVALID_JSON, C_PARSED, C_DS_FILTERED, C_DS_FAILEDEVAL,
+ C_OVERFLOW) = range(6)
 C_GLOBAL_N = 8
 CM_N = 8
 (CM_FILTER_IN, CM_FILTERED, CM_FAILEDEVAL, CM_UNDEF, CM_BADDATE,
  CM_TIME_OUT, CM_AGG_IN, CM_NONNUMERIC) = range(8)
 
 MAX_KEY = 8
-
-
-def _pad(n):
-    """Pad a chunk length so the cursor's 8-byte windows never read
-    past the buffer (>= 8 bytes of newline slack, 16B aligned)."""
-    return (n + 16 + 15) & ~15
 
 
 def _env_int(name, default):
@@ -204,7 +201,7 @@ class GpuEngine(object):
         agg_slots = _env_int("DRAGNET_AGG_SLOTS", 1 << 20)
         dict_slots = _env_int("DRAGNET_DICT_SLOTS", 1 << 20)
         dict_cap = max(len(blob) * 2 + (1 << 20), 8 << 20)
-        for attempt in range(2):
+        for _ in range(2):
             ctx = _ScanContext(self, cplan, agg_slots, dict_slots,
                                dict_cap, dense=False)
             ctx.state.columnar_query(descs, blob_t, vals_t, nrows, keep)
@@ -316,12 +313,28 @@ class _ScanContext(object):
             partials=partials, sdict=sdict, ndict=ndict,
             counters=self.counters)
 
-        self._partial = b""
-        self._pinned = None
-        self._copy_ev = None  # guards pinned-buffer reuse across chunks
         self.agg_slots = agg_slots
         self.dict_slots = dict_slots
         self._fin_stream = None  # lazy: D2H lane for pipelined decode
+
+        # Host staging state; None until the function named creates it.
+        # _ensure_buffers: chunk buffers + newline index, all modes
+        self._pinned = self._dev_data = None
+        self._pos = self._nlines = self._segs = None
+        # feed/flush: the one pinned buffer, copies on the current stream
+        self._partial = b""
+        self._copy_ev = None  # guards pinned-buffer reuse across chunks
+        # _ensure_file_staging: ping-pong buffers + copy stream
+        self._fs_pins = self._fs_dev = self._fs_done = None
+        self._fs_copy_stream = None
+        self._fs_idx = 0
+        # stage_resident: slices, slice events, pass ping-pong
+        self._resident = None  # (n, padded)
+        self._slices = self._slice_evs = self._slice_pos = None
+        self._copy_stream = self._dev_data_pp = self._pass_done = None
+        self._db_idx = 0
+        # stage_xpose: (xdata, wave_base, rec_len, n_slots)
+        self._x = None
 
     # ---- chunk feeding ----
 
@@ -348,8 +361,7 @@ class _ScanContext(object):
             return
         cap = max(padded, self.eng.chunk_bytes + (1 << 20))
         cap = (cap + 15) & ~15
-        self._pinned = torch.empty(cap, dtype=torch.uint8,
-                                   pin_memory=True)
+        self._pinned = torch.empty(cap, dtype=torch.uint8, pin_memory=True)
         self._dev_data = torch.empty(cap, dtype=torch.uint8, device=dev)
         # worst case: every byte is a newline
         self._pos = torch.empty(cap + 2, dtype=torch.int32, device=dev)
@@ -357,216 +369,102 @@ class _ScanContext(object):
         self._segs = torch.empty(cap // 2048 + 2, dtype=torch.int32,
                                  device=dev)
 
+    @staticmethod
+    def _pad_pinned(pin, n):
+        """Newline-pad pin[:n] (16B cursor window) -> padded length."""
+        padded = _pad(n)
+        pin[n:padded] = 10
+        return padded
+
+    def _index(self, dev_data, start, end):
+        """Newline index of dev_data[start:end] -> (pos, nlines)."""
+        self.eng.ops.newline_index(dev_data, start, end, self._segs,
+                                   self._pos, self._nlines)
+        return self._pos, self._nlines
+
+    def _submit(self, dev_data, start, end, index=None):
+        """Newline index (unless a pre-built one is given) + fused
+        scan of dev_data[start:end] on the current stream."""
+        pos, nlines = index or self._index(dev_data, start, end)
+        self.state.scan(dev_data, pos, nlines, start)
+
     def _run(self, buf):
         torch = self.t
         n = len(buf)
-        if n == 0:
-            return
-        padded = _pad(n)
-        self._ensure_buffers(padded)
+        self._ensure_buffers(_pad(n))
         pin = self._pinned
         # the previous chunk's async H2D copy must complete before the
         # pinned buffer is overwritten
-        if self._copy_ev is not None:
-            self._copy_ev.synchronize()
-        pin[:n] = torch.frombuffer(bytearray(buf), dtype=torch.uint8)
-        pin[n:padded] = 10  # newline padding for the 16B cursor window
-
-        dev_data = self._dev_data
-        dev_data[:padded].copy_(pin[:padded], non_blocking=True)
         if self._copy_ev is None:
             self._copy_ev = torch.cuda.Event()
+        else:
+            self._copy_ev.synchronize()
+        pin[:n] = torch.frombuffer(bytearray(buf), dtype=torch.uint8)
+        padded = self._pad_pinned(pin, n)
+        self._dev_data[:padded].copy_(pin[:padded], non_blocking=True)
         self._copy_ev.record()
-        self.eng.ops.newline_index(dev_data, 0, n, self._segs,
-                                   self._pos, self._nlines)
-        self.state.scan(dev_data, self._pos, self._nlines, 0)
+        self._submit(self._dev_data, 0, n)
 
     def overflowed(self):
-        return int(self.counters[5].item()) > 0
+        return int(self.counters[C_OVERFLOW].item()) > 0
 
     # ---- zero-copy file scanning ----
 
     def scan_files(self, files):
-        """Scan the concatenated bytes of `files` reading directly
-        into ping-pong pinned buffers (no intermediate Python bytes):
-        each chunk is cut at its last newline and the tail is carried
-        into the head of the other buffer while the GPU works on the
-        previous chunk.  Regular-file chunks are filled with parallel
-        preadv calls (page-cache/tmpfs reads are single-core bound
-        at ~10 GB/s; microbench 52/67/55 GB/s at 8/16/32 readers;
-        end-to-end scans measured most stable at 24 — the default.
-        DRAGNET_CHUNK_MB=1024 adds ~10% on >=50 GB scans at the cost
-        of slower pinned-buffer startup)."""
-        import concurrent.futures as cf
-        import stat as _stat
-
-        torch = self.t
+        """Scan the concatenated bytes of `files`, read directly into
+        ping-pong pinned buffers (no intermediate Python bytes):
+        chunks.frame_files fills and cuts one buffer while the GPU
+        works on the other.  (DRAGNET_CHUNK_MB=1024 adds ~10% on
+        >=50 GB scans at the cost of slower pinned-buffer startup.)"""
         cap = self.eng.chunk_bytes
-        # adaptive chunk size: big corpora amortize per-chunk overhead
-        # with 1 GiB chunks (+~10% measured at 24 readers); small scans
-        # keep the cheap-startup default
-        if (self._pinned is None
-                and os.environ.get("DRAGNET_CHUNK_MB") is None):
+        if self._pinned is None:  # buffers not sized yet
             try:
                 total = sum(os.stat(p).st_size for p in files)
             except OSError:
                 total = 0
-            if total > (16 << 30):
-                cap = self.eng.chunk_bytes = 1 << 30
-        if self._pinned is None:
-            self._ensure_buffers(_pad(cap))
-        pins = [self._pinned,
-                torch.empty(self._pinned.numel(), dtype=torch.uint8,
-                            pin_memory=True)]
-        views = [memoryview(p.numpy()) for p in pins]
-        evs = [None, None]
-        pool = cf.ThreadPoolExecutor(
-            max_workers=_env_int("DRAGNET_READERS", 24))
+            cap = choose_chunk_bytes(total, cap,
+                                     "DRAGNET_CHUNK_MB" in os.environ)
+        pins = self._ensure_file_staging(cap)
+        evs = [None, None]  # H2D-complete, per pinned buffer
 
-        def pread_full(fd, mv, off):
-            """preadv until mv is full (a single preadv may legally
-            return short; a short section would leave a HOLE of stale
-            bytes that corrupts record framing — observed at the
-            multi-GB scale)."""
-            done = 0
-            while done < len(mv):
-                got = os.preadv(fd, [mv[done:]], off + done)
-                if got <= 0:
-                    break
-                done += got
-            return done
+        def wait(i):
+            if evs[i] is not None:
+                evs[i].synchronize()
+                evs[i] = None
 
-        def fill_from(fd, fpos, fsize, view, at, want, seq_file):
-            """Read up to `want` bytes of fd@fpos into view[at:].
-            Returns bytes read (contiguous).  Parallel preadv for
-            regular files."""
-            want = min(want, fsize - fpos)
-            if want <= 0:
-                return 0
-            if seq_file is not None:  # char device / pipe: sequential
-                return seq_file.readinto(view[at:at + want]) or 0
-            if want < (8 << 20):
-                return pread_full(fd, view[at:at + want], fpos)
-            nsec = _env_int("DRAGNET_READERS", 24)
-            sec = (want + nsec - 1) // nsec
-            futs = []
-            for s in range(0, want, sec):
-                e = min(s + sec, want)
-                futs.append((e - s, pool.submit(
-                    pread_full, fd, view[at + s:at + e], fpos + s)))
-            # only the contiguous prefix counts
-            total = 0
-            for length, fut in futs:
-                got = fut.result()
-                total += got
-                if got < length:
-                    break
-            return total
-
-        def last_newline(buf, n):
-            probe = max(0, n - (1 << 16))
-            cut = bytes(buf[probe:n]).rfind(b"\n")
-            if cut >= 0:
-                return probe + cut
-            return bytes(buf[:probe]).rfind(b"\n")
-
-        cur = 0
-        head = 0
-        fiter = iter(files)
-        fobj = None     # (fd, pos, size, seq_file or None)
+        frames = frame_files(files, [memoryview(p.numpy()) for p in pins],
+                             cap, wait, _env_int("DRAGNET_READERS", 24))
         try:
-            while True:
-                if evs[cur] is not None:
-                    evs[cur].synchronize()
-                    evs[cur] = None
-                n = head
-                eof = False
-                while n < cap:
-                    if fobj is None:
-                        try:
-                            path = next(fiter)
-                        except StopIteration:
-                            eof = True
-                            break
-                        st = os.stat(path)
-                        if _stat.S_ISREG(st.st_mode):
-                            fd = os.open(path, os.O_RDONLY)
-                            fobj = (fd, 0, st.st_size, None)
-                        else:
-                            sf = open(path, "rb", buffering=0)
-                            fobj = (sf.fileno(), 0, 1 << 62, sf)
-                    fd, fpos, fsize, sf = fobj
-                    got = fill_from(fd, fpos, fsize, views[cur], n,
-                                    cap - n, sf)
-                    if got <= 0:
-                        if sf is not None:
-                            sf.close()
-                        else:
-                            os.close(fd)
-                        fobj = None
-                        continue
-                    fobj = (fd, fpos + got, fsize, sf)
-                    n += got
-                if n == 0:
-                    break
-                cut = last_newline(views[cur], n)
-                if eof and cut < n - 1:
-                    views[cur][n:n + 1] = b"\n"
-                    n += 1
-                    cut = n - 1
-                nxt = 1 - cur
-                if cut < 0:
-                    if n >= cap:
-                        raise RuntimeError(
-                            "record exceeds the chunk buffer (%d "
-                            "bytes); raise DRAGNET_CHUNK_MB" % cap)
-                    tail = n
-                else:
-                    tail = n - (cut + 1)
-                # the tail must be carried over BEFORE the chunk is
-                # launched: _run_pinned pads pin[cut+1:] with newlines
-                # and would clobber the carried bytes (record-splitting
-                # corruption observed at multi-GB scale)
-                if tail:
-                    if evs[nxt] is not None:
-                        evs[nxt].synchronize()
-                        evs[nxt] = None
-                    views[nxt][:tail] = views[cur][n - tail:n]
-                if cut >= 0:
-                    evs[cur] = self._run_pinned(pins[cur], cut + 1)
-                head = tail
-                cur = nxt
-                if eof:
-                    break
+            for i, n in frames:
+                evs[i] = self._run_pinned(pins[i], n)
         finally:
-            if fobj is not None:
-                _fd, _p, _s, sf = fobj
-                if sf is not None:
-                    sf.close()
-                else:
-                    os.close(_fd)
-            pool.shutdown(wait=False)
+            frames.close()  # descriptors + reader pool
 
-    def _run_pinned(self, pin, n):
-        """H2D + kernels for pin[:n] (already newline-terminated).
-
-        Ping-pong DEVICE buffers with the H2D on a dedicated copy
-        stream: chunk k+1's copy overlaps chunk k's kernels, so the
-        steady state is max(fill, copy, kernels) instead of their sum
-        (the serial form measured 12-15 GB/s end-to-end vs the 67 GB/s
-        the parallel readers deliver; see profiles/r02 notes).
-        Returns the H2D-complete event — the caller must wait on it
-        before refilling this pinned buffer."""
+    def _ensure_file_staging(self, cap):
+        """Ping-pong pinned and DEVICE buffers with the H2D on a
+        dedicated copy stream: chunk k+1's copy overlaps chunk k's
+        kernels, so the steady state is max(fill, copy, kernels)
+        instead of their sum (serial: 12-15 GB/s end-to-end vs the
+        67 GB/s the readers deliver; profiles/r02).  Returns the pins."""
         torch = self.t
-        padded = _pad(n)
-        pin[n:padded] = 10
-        if not hasattr(self, "_fs_dev"):
+        if self._fs_pins is None:
+            if self._pinned is None:
+                self._ensure_buffers(_pad(cap))
+            self._fs_pins = [self._pinned, torch.empty(
+                self._pinned.numel(), dtype=torch.uint8, pin_memory=True)]
             self._fs_copy_stream = torch.cuda.Stream(
                 device=self.eng.device)
             self._fs_dev = [self._dev_data,
                             torch.empty_like(self._dev_data)]
             self._fs_done = [torch.cuda.Event(), torch.cuda.Event()]
-            self._fs_idx = 0
+        return self._fs_pins
+
+    def _run_pinned(self, pin, n):
+        """H2D + kernels for pin[:n] (already newline-terminated).
+        Returns the H2D-complete event — the caller must wait on it
+        before refilling this pinned buffer."""
+        torch = self.t
+        padded = self._pad_pinned(pin, n)
         idx = self._fs_idx
         self._fs_idx ^= 1
         dev_data = self._fs_dev[idx]
@@ -579,9 +477,7 @@ class _ScanContext(object):
             dev_data[:padded].copy_(pin[:padded], non_blocking=True)
             ev.record(cs)
         main.wait_event(ev)
-        self.eng.ops.newline_index(dev_data, 0, n, self._segs,
-                                   self._pos, self._nlines)
-        self.state.scan(dev_data, self._pos, self._nlines, 0)
+        self._submit(dev_data, 0, n)
         self._fs_done[idx].record(main)
         return ev
 
@@ -597,28 +493,18 @@ class _ScanContext(object):
         if n_slices is None:
             n_slices = _env_int("DRAGNET_SLICES", 6)
         n = len(buf)
-        padded = _pad(n)
-        self._ensure_buffers(padded)
+        self._ensure_buffers(_pad(n))
         pin = self._pinned
         pin[:n] = torch.frombuffer(bytearray(buf), dtype=torch.uint8)
-        pin[n:padded] = 10
+        padded = self._pad_pinned(pin, n)
 
         # newline-aligned slice boundaries
-        bounds = [0]
-        for k in range(1, n_slices):
-            target = n * k // n_slices
-            cut = buf.rfind(b"\n", 0, target)
-            start = cut + 1 if cut >= 0 else 0
-            if start > bounds[-1]:
-                bounds.append(start)
-        bounds.append(n)
-        self._slices = [(bounds[i], bounds[i + 1])
-                        for i in range(len(bounds) - 1)
-                        if bounds[i + 1] > bounds[i]]
+        bounds = sorted({0, n} | {buf.rfind(b"\n", 0, n * k // n_slices) + 1
+                                  for k in range(1, n_slices)})
+        self._slices = list(zip(bounds, bounds[1:]))
         self._resident = (n, padded)
         self._copy_stream = torch.cuda.Stream(device=self.eng.device)
-        self._slice_evs = [torch.cuda.Event()
-                           for _ in self._slices]
+        self._slice_evs = [torch.cuda.Event() for _ in self._slices]
         # Ping-pong device pools for streaming passes: pass k+1's H2D
         # lands in the buffer pass k is NOT reading, so the copy
         # stream runs back-to-back at link rate instead of stalling
@@ -634,12 +520,9 @@ class _ScanContext(object):
         self._dev_data[:padded].copy_(pin[:padded])
         self._slice_pos = []
         for (s, e) in self._slices:
-            self.eng.ops.newline_index(self._dev_data, s, e,
-                                       self._segs, self._pos,
-                                       self._nlines)
-            cnt = int(self._nlines.item())
+            pos, nlines = self._index(self._dev_data, s, e)
             self._slice_pos.append(
-                (self._pos[:cnt].clone(), self._nlines.clone()))
+                (pos[:int(nlines.item())].clone(), nlines.clone()))
 
     def scan_resident(self, h2d=True):
         """One full streaming pass over the staged pool: sliced async
@@ -670,18 +553,13 @@ class _ScanContext(object):
                     self._slice_evs[k].record(self._copy_stream)
         # kernels per slice on the compute stream.  Streaming passes
         # (h2d=True) model fresh data and re-index newlines each pass;
-        # device-resident re-scans reuse the staged line index (a
-        # re-scanning engine retains it like the reference retains its
-        # on-disk indexes).
+        # device-resident re-scans reuse the staged line index.
         for k, (s, e) in enumerate(self._slices):
             if h2d:
                 main.wait_event(self._slice_evs[k])
-                self.eng.ops.newline_index(dev_data, s, e, self._segs,
-                                           self._pos, self._nlines)
-                self.state.scan(dev_data, self._pos, self._nlines, s)
+                self._submit(dev_data, s, e)
             else:
-                pos_k, nlines_k = self._slice_pos[k]
-                self.state.scan(dev_data, pos_k, nlines_k, s)
+                self._submit(dev_data, s, e, self._slice_pos[k])
         if h2d:
             ev_done.record(main)  # last reader of this pass's buffer
 
@@ -700,28 +578,27 @@ class _ScanContext(object):
         cumsum + the xpose_build_kernel scatter) — no host staging
         pass.  DRAGNET_XPOSE_HOST=1 selects the r1 numpy builder
         (A/B + layout unit tests)."""
-        if os.environ.get("DRAGNET_XPOSE_HOST") == "1":
-            return self._stage_xpose_host(buf)
-        torch = self.t
-        dev = self.eng.device
         gran = _env_int("DRAGNET_XGRAN", 64)
         if gran not in (32, 64, 128):
             # the scan kernel is templated on the granule size; an
             # unsupported value would mismatch the staged layout
             raise ValueError("DRAGNET_XGRAN must be 32, 64 or 128")
+        if os.environ.get("DRAGNET_XPOSE_HOST") == "1":
+            return self._stage_xpose_host(buf, gran)
+        torch = self.t
+        dev = self.eng.device
         glog = gran.bit_length() - 1
-        if not hasattr(self, "_resident"):
+        if self._resident is None:
             if buf is None:
                 raise ValueError("no resident pool to transpose")
             self.stage_resident(buf)
         n, _padded = self._resident
         # full-pool line index (the staged slice indexes cover slices)
-        self.eng.ops.newline_index(self._dev_data, 0, n, self._segs,
-                                   self._pos, self._nlines)
-        nrec = int(self._nlines.item())  # one-time staging sync
+        pos, nlines = self._index(self._dev_data, 0, n)
+        nrec = int(nlines.item())  # one-time staging sync
         if nrec == 0:
             raise ValueError("no records")
-        pos = self._pos[:nrec].to(torch.int64)
+        pos = pos[:nrec].to(torch.int64)
         starts = torch.empty_like(pos)
         starts[0] = 0
         starts[1:] = pos[:-1] + 1
@@ -746,37 +623,23 @@ class _ScanContext(object):
         xb = torch.empty(total, dtype=torch.uint8, device=dev)
         self.eng.ops.xpose_build(self._dev_data, sstart, slot_len,
                                  wbase, nslots, glog, xb)
-        self._x = {
-            "xdata": xb,
-            "wave_base": wbase,  # kernel reads [0, nw); +1 harmless
-            "rec_len": slot_len,
-            "n_slots": nslots,
-        }
-        self._x_nrec = nrec
+        # the kernel reads wave_base[0, nw); the +1 entry is harmless
+        self._x = (xb, wbase, slot_len, nslots)
 
-    def _stage_xpose_host(self, buf):
+    def _stage_xpose_host(self, buf, gran):
         """r1 host-side numpy builder (kept for A/B and layout tests)."""
         torch = self.t
         dev = self.eng.device
-        gran = _env_int("DRAGNET_XGRAN", 64)
-        if gran not in (32, 64, 128):
-            raise ValueError("DRAGNET_XGRAN must be 32, 64 or 128")
-        xb, wave_base, slot_len, nslots, n = _build_xpose_layout(
+        xb, wave_base, slot_len, nslots, _n = _build_xpose_layout(
             buf, gran)
-        self._x = {
-            "xdata": torch.from_numpy(xb).to(dev),
-            "wave_base": torch.from_numpy(wave_base).to(dev),
-            "rec_len": torch.from_numpy(
-                slot_len.view(np.int32)).to(dev),
-            "n_slots": nslots,
-        }
-        self._x_nrec = n
+        self._x = (torch.from_numpy(xb).to(dev),
+                   torch.from_numpy(wave_base).to(dev),
+                   torch.from_numpy(slot_len.view(np.int32)).to(dev),
+                   nslots)
 
     def scan_xpose(self):
         """One scan pass over the wave-transposed staging."""
-        x = self._x
-        self.state.scan_xpose(x["xdata"], x["wave_base"], x["rec_len"],
-                              x["n_slots"])
+        self.state.scan_xpose(*self._x)
 
     def make_graph(self, h2d=True, xpose=False):
         """Capture reset + the whole scan pass into a hipGraph so a
@@ -896,22 +759,20 @@ class _ScanContext(object):
         """Reconstruct the reference pipeline counter stages from the
         device counters (mirrors scan_cpu.ScanPipeline.counter_stages)."""
         cp = self.cplan
+        parsed = int(cnt[C_PARSED])
         stages = [("json parser", {
-            "ninputs": int(cnt[0]), "noutputs": int(cnt[2]),
-            "invalid json": int(cnt[1])})]
+            "ninputs": int(cnt[C_LINES]), "noutputs": parsed,
+            "invalid json": int(cnt[C_INVALID_JSON])})]
         if cp.data_format == "json":
             stages.append(("SkinnerAdapterStream",
-                           {"ninputs": int(cnt[2]),
-                            "noutputs": int(cnt[2])}))
-        # program 0 is the ds filter; OP_TRUE (8) means "no filter"
+                           {"ninputs": parsed, "noutputs": parsed}))
+        # program 0 is the ds filter; OP_TRUE means "no filter"
         progs, bounds = cp.programs
-        if progs[bounds[0][0]][0] != 8:
-            n_in = int(cnt[2])
+        if progs[bounds[0][0]][0] != planmod.OP_TRUE:
+            out, err = int(cnt[C_DS_FILTERED]), int(cnt[C_DS_FAILEDEVAL])
             stages.append(("Datasource filter", {
-                "ninputs": n_in,
-                "noutputs": n_in - int(cnt[3]) - int(cnt[4]),
-                "nfilteredout": int(cnt[3]),
-                "nfailedeval": int(cnt[4])}))
+                "ninputs": parsed, "noutputs": parsed - out - err,
+                "nfilteredout": out, "nfailedeval": err}))
         # metric 0's pipeline (what the CLI displays for scans)
         q = queries[0]
         mc = cnt[C_GLOBAL_N:C_GLOBAL_N + CM_N]
@@ -923,22 +784,19 @@ class _ScanContext(object):
                 "nfilteredout": int(mc[CM_FILTERED]),
                 "nfailedeval": int(mc[CM_FAILEDEVAL])}))
             n = out
-        metrics, _sreq = cp.metrics
-        if metrics[0][3] > 0:  # has synthetic requirements
+        m0 = cp.metrics[0][0]
+        if m0[planmod.M_NSYNTH] > 0:  # has synthetic requirements
             out = n - int(mc[CM_UNDEF]) - int(mc[CM_BADDATE])
             stages.append(("Datetime parser", {
                 "ninputs": n, "noutputs": out,
                 "undef": int(mc[CM_UNDEF]),
                 "baddate": int(mc[CM_BADDATE])}))
             n = out
-        if metrics[0][5]:  # time filter
-            out = n - int(mc[CM_TIME_OUT])
+        if m0[planmod.M_HAS_TF]:  # time filter
             stages.append(("Time filter", {
-                "ninputs": n, "noutputs": out,
+                "ninputs": n, "noutputs": n - int(mc[CM_TIME_OUT]),
                 "nfilteredout": int(mc[CM_TIME_OUT]),
                 "nfailedeval": 0}))
-            n = out
-        self._agg_stage_n = n
         stages.append(("Aggregator", {
             "ninputs": int(mc[CM_AGG_IN]),
             "noutputs": 0,  # patched by caller if needed

@@ -54,6 +54,11 @@ MAX_FIELDS = 24
 MAX_DEPTH = 12
 MAX_KEY = 8  # device key tuple width (common.h / gpu.py)
 
+# metric row columns (CompiledPlan.metrics[0], i32 [n_metrics, M_N])
+(M_PROG, M_NBD, M_BD_OFF, M_NSYNTH, M_SYNTH_OFF, M_HAS_TF, M_T_GE,
+ M_T_LT) = range(8)
+M_N = 8
+
 
 def fnv1a(data, h=FNV_OFFSET):
     for b in data:
@@ -344,11 +349,11 @@ def compile_plan(queries, ds_filter=None, time_field=None,
             bd_rows.append([kind, ref, bkind, 0])
             bd_steps.append(step)
 
-        metric_rows.append([
-            prog_id, len(q.breakdowns), bd_off,
-            len(my_synth_u), sreq_off, has_tf,
-            int(t_ge), int(t_lt),
-        ])
+        row = {M_PROG: prog_id, M_NBD: len(q.breakdowns),
+               M_BD_OFF: bd_off, M_NSYNTH: len(my_synth_u),
+               M_SYNTH_OFF: sreq_off, M_HAS_TF: has_tf,
+               M_T_GE: int(t_ge), M_T_LT: int(t_lt)}
+        metric_rows.append([row[c] for c in range(M_N)])
 
     # json-skinner: top-level "value" (weight) and "fields" (presence
     # check), both outside the "fields." prefix
@@ -409,7 +414,7 @@ def compile_plan(queries, ds_filter=None, time_field=None,
     const_bytes = np.frombuffer(
         bytes(consts.bytes) or b"\0", dtype=np.uint8).copy()
     synthetic = np.array(synth_slots or [0], dtype=np.int32)
-    metrics = np.array(metric_rows, dtype=np.int32).reshape(-1, 8)
+    metrics = np.array(metric_rows, dtype=np.int32).reshape(-1, M_N)
     bds = np.array(bd_rows or [[0, 0, 0, 0]],
                    dtype=np.int32).reshape(-1, 4)
     steps = np.array(bd_steps or [0.0], dtype=np.float64)

@@ -459,6 +459,50 @@ def test_many_chunk_boundaries(engines, tmp_path):
     assert g.aggregators[0].points() == c.aggregators[0].points()
 
 
+def test_record_at_chunk_limit(engines, tmp_path):
+    """256-byte chunks over two files (the first without a trailing
+    newline, so its last record runs into the second file): a 255-byte
+    record is the longest that fits and scans exactly; one byte more is
+    refused.  The scan leaves the engine's chunk size alone."""
+    import json as _json
+
+    cpu, gpu = engines
+    from dragnet_amd.query import query_load
+
+    def record(i, size=None):
+        r = _json.dumps({"m": "m%d" % (i % 5), "i": i})
+        if size is not None:
+            r = r[:-1] + ', "p": "%s"}'
+            r = r % ("x" * (size - len(r) + 2))
+            assert len(r) == size
+        return r.encode()
+
+    def write(big):
+        recs = [record(i) for i in range(200)]
+        recs[57] = record(57, big)
+        a, b = tmp_path / ("a%d.log" % big), tmp_path / ("b%d.log" % big)
+        a.write_bytes(b"\n".join(recs[:100]) + b'\n{"m": "split", ')
+        b.write_bytes(b'"i": -1}\n' + b"\n".join(recs[100:]) + b"\n")
+        return [str(a), str(b)]
+
+    q = query_load(breakdown_specs="m")
+    old = gpu.chunk_bytes
+    try:
+        gpu.chunk_bytes = 256
+        files = write(255)
+        g = gpu.scan(files, [q])
+        assert gpu.chunk_bytes == 256
+        with pytest.raises(RuntimeError,
+                           match="record exceeds the chunk buffer"):
+            gpu.scan(write(256), [q])
+    finally:
+        gpu.chunk_bytes = old
+    c = cpu.scan(files, [q])
+    assert g.aggregators[0].points() == c.aggregators[0].points()
+    assert dict(g.stages)["json parser"] == dict(c.stages)["json parser"]
+    assert dict(g.stages)["json parser"]["ninputs"] == 201
+
+
 def test_dense_mfma_vs_hash_path(engines, tmp_path):
     """The dense-accumulation path (slot directory + per-workgroup
     partial matrix + MFMA f64 column-sum reduce) must equal the atomic

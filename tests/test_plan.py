@@ -36,6 +36,15 @@ def test_constants_match_header():
     assert cval("SPECIAL_UNDEF") == plan.SPECIAL_UNDEF
     assert cval("MAX_FIELDS") == plan.MAX_FIELDS
 
+    # device counter slots (CounterSlot) as the GPU engine indexes them
+    from dragnet_amd.engine import gpu
+    for name in ("C_LINES", "C_INVALID_JSON", "C_PARSED",
+                 "C_DS_FILTERED", "C_DS_FAILEDEVAL", "C_OVERFLOW",
+                 "C_GLOBAL_N", "CM_FILTER_IN", "CM_FILTERED",
+                 "CM_FAILEDEVAL", "CM_UNDEF", "CM_BADDATE",
+                 "CM_TIME_OUT", "CM_AGG_IN", "CM_NONNUMERIC", "CM_N"):
+        assert cval(name) == getattr(gpu, name), name
+
 
 def test_lds_layout_pinned():
     """The kernels' dynamic-LDS size is byte-for-byte fixed (occupancy
