@@ -8,7 +8,7 @@ packed little buffers the fused HIP scan kernel consumes:
     (filter fields + breakdown sources + synthetic date sources), as
     64-bit FNV-1a signatures of the dotted path.  The device parser
     computes the same incremental signature while walking each record's
-    nesting (dragnet_amd/ops/hip/scan_kernels.hip, K1) — dotted literal
+    nesting (dragnet_amd/ops/hip/scan_record.h, K1) — dotted literal
     keys and nested paths collapse to the same signature by
     construction, mirroring the CPU lookup (points.lookup).
   * predicate programs: prefix-tree bytecode with subtree skip offsets
@@ -82,7 +82,7 @@ SIG_LIT_MARK = 0xC2B2AE3D27D4EB4F  # fields-root literal-dotted marker
 
 def _sig_mix(x):
     """5-op bijective mix used ONLY for path signatures (mirrors
-    scan_kernels.hip sig_mix)."""
+    ops/hip/scan_text.h sig_mix)."""
     x &= MASK64
     x ^= x >> 32
     x = (x * 0xD6E8FEB86659FD93) & MASK64
@@ -93,7 +93,7 @@ def comp_into(sig, b):
     """Fold one path component's bytes into the chained signature:
     zero-padded 8-byte little-endian words, one mix per word, plus a
     length-finalization mix — computable on-device with inline SWAR
-    window folds during the key scan (scan_kernels.hip scan_key_sig /
+    window folds during the key scan (ops/hip/scan_text.h scan_key_sig /
     sig_comp_finish must produce identical values)."""
     for k in range(0, len(b), 8):
         w = int.from_bytes(b[k:k + 8].ljust(8, b"\0"), "little")

@@ -1,9 +1,14 @@
 // Shared device-plan layout constants for the dragnet_amd HIP engine.
 // Mirrored by dragnet_amd/engine/plan.py — keep in sync (tested by
 // tests/test_plan.py::test_constants_match).
+// Includable by a plain host compiler too (no ROCm header needed).
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#endif
+#include <cstddef>
 #include <cstdint>
+#include "hd.h"
 
 namespace dn {
 
@@ -48,7 +53,7 @@ constexpr uint32_t SPECIAL_NULL = 0, SPECIAL_UNDEF = 1,
                    SPECIAL_ARRJSON = 6;  // | (string-dict id << 3)
 constexpr uint32_t EMPTY_CODE = 0xFFFFFFFFu;
 
-inline __device__ __host__ uint32_t make_code(uint32_t tag, uint32_t val) {
+inline DN_HD uint32_t make_code(uint32_t tag, uint32_t val) {
   return (tag << 30) | (val & 0x3FFFFFFFu);
 }
 

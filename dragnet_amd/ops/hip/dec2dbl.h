@@ -27,15 +27,7 @@
 #include <stdint.h>
 #include <string.h>
 
-#if defined(__HIPCC__)
-#define DN_HD __host__ __device__
-#define DN_HD_INLINE __host__ __device__ __forceinline__
-#define DN_HD_NOINLINE __host__ __device__ __attribute__((noinline))
-#else
-#define DN_HD
-#define DN_HD_INLINE inline
-#define DN_HD_NOINLINE __attribute__((noinline))
-#endif
+#include "hd.h"
 
 #if defined(__HIP_DEVICE_COMPILE__)
 #define DN_TABLE_QUAL static __device__ const

@@ -20,7 +20,6 @@ device keeps 19 digits, so the result is float(L) or one of its two
 neighbours — the one divergence that stays documented.
 """
 
-import calendar
 import datetime
 import json
 import math
@@ -28,6 +27,8 @@ import math
 import pytest
 
 import numeric_cases as nc
+from numeric_cases import (EPOCH, civil_ms, date_cases, geometry_records,
+                           string_cases)
 
 pytestmark = pytest.mark.gpu
 
@@ -161,40 +162,6 @@ def test_infinity_literals_drop_under_a_bucketizer(engines, tmp_path):
 
 # ---- SWAR digit-run geometry -----------------------------------------
 
-TERMS = [",", "}", " ", "e5", ".5"]
-
-
-def geometry_records():
-    """Digit runs of every length 1..24 as the integer part and as the
-    fraction part, at every byte alignment 0..7 (a preceding string
-    value pads the record), followed by each terminator; digits all
-    '9' and '1' followed by zeros.  Returns [(line, literal|None)]:
-    None where the text is not a JSON number (fraction run + '.5')."""
-    recs = []
-    k = 0
-    for part in ("int", "frac"):
-        for n in range(1, 25):
-            for run in ("9" * n, "1" + "0" * (n - 1)):
-                for align in range(8):
-                    for term in TERMS:
-                        lit = run if part == "int" else "3." + run
-                        valid = True
-                        if term in ("e5", ".5"):
-                            lit += term
-                            valid = not (part == "frac" and term == ".5")
-                        if term == ",":
-                            tail = ', "z": 1}'
-                        elif term == " ":
-                            tail = " }"
-                        else:
-                            tail = "}"
-                        line = '{"id": "%d", "p": "%s", "n": %s%s' % (
-                            k, "x" * align, lit, tail)
-                        recs.append((line, lit if valid else None))
-                        k += 1
-    return recs
-
-
 def test_digit_run_geometry(engines, tmp_path):
     recs = geometry_records()
     assert len(recs) <= 4000 * 2
@@ -297,47 +264,6 @@ def test_literal_classes_lds_staged(engines, tmp_path, class_corpus,
 
 
 # ---- js_to_number ----------------------------------------------------
-
-# (raw JSON text of the string value, Number(value) per ECMAScript)
-_NAN = float("nan")
-ESCAPED_SPELLINGS = [
-    ('"\\t12"', 12.0), ('"12\\n"', 12.0), ('"\\u002012"', 12.0),
-    ('"\\r\\n 12 \\t\\f"', 12.0), ('"\\u000b12\\u000C"', 12.0),
-    ('"\\u00a012\\ufeff"', 12.0), ('"\\u2003 12\\u2028"', 12.0),
-    ('"12\\\\t"', _NAN),       # 12 + backslash + t: no whitespace
-    ('"12\\\\\\t"', _NAN),     # 12 + backslash + TAB: inner backslash
-    ('"\\\\t12"', _NAN), ('"1\\t2"', _NAN), ('"\\u00412"', _NAN),
-    ('"\\t"', 0.0), ('"\\u0020\\n"', 0.0), ('"12\\u001c"', _NAN),
-    ('"12\\u0085"', _NAN), ('"\\b12"', _NAN),
-]
-
-
-def string_cases():
-    """[(raw JSON string text, truth double)]: the V8-recorded table,
-    the escaped-whitespace spellings, and the 17-digit / leading-zero
-    literal classes spelled as strings — plain, and scaled by an
-    exponent so the value is an integer beyond 2^53 where a
-    step-1 lquantize shows every bit."""
-    cases = []
-    for s, want in nc.load_golden()["tonumber"]:
-        v = _NAN if want == "NaN" else nc.bits_to_double(want)
-        cases.append((json.dumps(s), v))
-    cases += ESCAPED_SPELLINGS
-    cls = nc.literal_classes(per_class=150, seed=77)
-    for lit in cls["repr_1e6"] + cls["repr_unit"] + cls["leading_zero"]:
-        cases.append(('"%s"' % lit, float(lit)))
-    for lit in cls["d16_small_exp"]:
-        m = lit.partition("e")[0]
-        for e in (17, 18):
-            cases.append(('"%se%d"' % (m, e), float("%se%d" % (m, e))))
-    for lit in cls["leading_zero"]:
-        frac = lit[2:]
-        s = "%se%d" % (lit, len(frac) + 3)
-        cases.append(('" %s"' % s, float(s)))
-    for t in nc.tie_literals():
-        cases.append(('"%s"' % t, float(t)))
-    return cases
-
 
 def string_lines(cases):
     return b"".join(('{"id": "%d", "s": %s}\n' % (i, raw)).encode()
@@ -487,93 +413,6 @@ def test_filter_boundaries(engines, tmp_path, const):
 
 
 # ---- dates (K3) ------------------------------------------------------
-
-EPOCH = datetime.datetime(1970, 1, 1)
-
-
-def civil_ms(y, mo, d, hh=0, mi=0, ss=0, ms=0, tz_min=0):
-    """Epoch ms by datetime arithmetic, or None if a component is out
-    of range (ES5 rules: hour 24 only as 24:00:00.000).  Year 0 does
-    not exist in datetime: shift by one 400-year Gregorian cycle."""
-    shift = 0
-    if y < 1:
-        y += 400
-        shift = 146097
-    if not (1 <= mo <= 12) or not (1 <= d <= calendar.monthrange(y, mo)[1]):
-        return None
-    if hh > 24 or mi > 59 or ss > 59 or (hh == 24 and (mi or ss or ms)):
-        return None
-    days = (datetime.datetime(y, mo, d) - EPOCH).days - shift
-    return (((days * 24 + hh) * 60 + mi) * 60 + ss) * 1000 + ms \
-        - tz_min * 60000
-
-
-def date_cases():
-    """[(string, epoch ms | None)]."""
-    out = []
-    for y in (1900, 2000, 2016, 2100):
-        for mo in range(0, 14):
-            last = calendar.monthrange(y, mo)[1] if 1 <= mo <= 12 else 31
-            days = range(0, last + 2) if 1 <= mo <= 12 else (1, 15)
-            for d in days:
-                out.append(("%04d-%02d-%02dT06:07:08.009Z" % (y, mo, d),
-                            civil_ms(y, mo, d, 6, 7, 8, 9)))
-    base = (2014, 5, 1)
-    for hh in (0, 23, 24, 25):
-        for mi in (0, 59, 60):
-            for ss in (0, 59, 60):
-                out.append(("2014-05-01T%02d:%02d:%02dZ" % (hh, mi, ss),
-                            civil_ms(*base, hh, mi, ss)))
-    out.append(("2014-05-01T24:00:00.000Z", civil_ms(*base, 24)))
-    out.append(("2014-05-01T24:00:00.001Z", None))
-    out.append(("2014-12-31T24:00:00", civil_ms(2015, 1, 1)))
-    digits = "7891234567"
-    for n in range(0, 11):
-        frac = digits[:n]
-        want = civil_ms(*base, 12, 34, 56, int((frac + "000")[:3])) \
-            if 1 <= n <= 9 else None
-        out.append(("2014-05-01T12:34:56.%sZ" % frac, want))
-    out.append(("2014-05-01T12:34:56.9999", civil_ms(*base, 12, 34, 56, 999)))
-    t = civil_ms(*base, 12, 34, 56, 789)
-    for zone, tzm in (("Z", 0), ("+05:30", 330), ("+0530", 330),
-                      ("-00:00", 0), ("", 0), ("-08:00", -480),
-                      ("+14:00", 840)):
-        out.append(("2014-05-01T12:34:56.789" + zone, t - tzm * 60000))
-        out.append(("2014-05-01T12:34" + zone,
-                    civil_ms(*base, 12, 34) - tzm * 60000))
-    out += [
-        ("2014-05-01Z", None), ("2014-05-01+05:30", None),
-        ("2014-05Z", None), ("2014Z", None),
-        ("2014-05-01T12:34:56+5:30", None), ("2014-05-01T12:34:56+05", None),
-        ("2014-05-01T12:34:56 Z", None),
-        ("2014", civil_ms(2014, 1, 1)), ("2014-05", civil_ms(2014, 5, 1)),
-        ("2014-05-01", civil_ms(*base)),
-        ("2014-05-01 12:34:56", civil_ms(*base, 12, 34, 56)),
-        ("2014-05-01T12:34:56", civil_ms(*base, 12, 34, 56)),
-        ("2014-05-01t12:34:56Z", None), ("2014-05-01T12:34:56z", None),
-        ("2014-05-01T12", None), ("2014-05-01T12:3", None),
-        ("2014-5-01", None), ("14-05-01", None), ("20140501", None),
-        ("2014-05-01T", None), ("", None), ("   ", None),
-        (" 2014-05-01T12:34:56Z", civil_ms(*base, 12, 34, 56)),
-        ("2014-05-01T12:34:56Z ", civil_ms(*base, 12, 34, 56)),
-        ("\t2014-05-01T12:34:56Z\t", civil_ms(*base, 12, 34, 56)),
-        (" \t 2014-05-01 \n", civil_ms(*base)),
-        ("\\t2014-05-01", None),   # a literal backslash, not a tab
-        ("2014-05-01\\", None),
-        ("0000-01-01T00:00:00Z", civil_ms(0, 1, 1)),
-        ("0000-02-29T00:00:00Z", civil_ms(0, 2, 29)),
-        ("0000-12-31T23:59:59.999Z", civil_ms(0, 12, 31, 23, 59, 59, 999)),
-        ("1969-12-31T23:59:59.500Z", -500),
-        ("1969-12-31T23:59:59.999Z", -1), ("1969-12-31T23:59:59Z", -1000),
-        ("1969-12-31T23:59:58.001Z", -1999),
-        ("1969-07-20T20:17:40Z", civil_ms(1969, 7, 20, 20, 17, 40)),
-        ("1970-01-01T00:00:00.000Z", 0), ("1970-01-01T00:00:00.999Z", 999),
-        ("9999-12-31T23:59:59.999Z",
-         civil_ms(9999, 12, 31, 23, 59, 59, 999)),
-        ("1970-01-01T00:00:00+00:01", -60000),
-    ]
-    return out
-
 
 def date_lines(cases):
     return b"".join(
