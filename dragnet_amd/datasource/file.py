@@ -64,13 +64,20 @@ class ScanResult(object):
     """A scan's output: per-query aggregators + counter stages.
 
     nonroot marks an empty result on a non-rank-0 process of a
-    distributed scan (the CLI suppresses output for these)."""
+    distributed scan (the CLI suppresses output for these).
 
-    def __init__(self, aggregators, stages, files=None, nonroot=False):
+    gpu_stats (GPU engine scans; empty otherwise) tells how the scan
+    coped with its table sizes: "restarts" (whole-scan reruns), and
+    in-place growths per structure — "agg" (a list, per metric),
+    "sdict", "sdata", "ndict"."""
+
+    def __init__(self, aggregators, stages, files=None, nonroot=False,
+                 gpu_stats=None):
         self.aggregators = aggregators
         self.stages = stages
         self.files = files or []
         self.nonroot = nonroot
+        self.gpu_stats = gpu_stats or {}
 
 
 class FileDatasource(object):

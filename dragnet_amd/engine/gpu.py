@@ -10,18 +10,25 @@ CPU oracle produces (points.Aggregator) — so every downstream consumer
 (formatters, index sink, RCCL merge) is engine-agnostic.  File scans
 take their chunks from the host-only framer in engine/chunks.py.
 
-Capacity handling: the hash tables and dictionaries are sized up front;
-on overflow (C_OVERFLOW counter) the whole scan is retried with 8x the
-capacity (aggregation is a pure function of the input, so a restart is
-correct).
+Capacity handling: the hash tables and dictionaries are sized up front,
+as a first guess.  A scan of regular files restarts on overflow
+(C_OVERFLOW counter) with 8x the capacity (aggregation is a pure
+function of the input, so a restart is correct).  A scan that cannot
+be read twice (byte source, pipe, device) — or any scan under
+DRAGNET_GROW=1 — is growable instead: engine/capacity.py plans every
+launch so that nothing can overflow, and a structure that is about to
+fill is rehashed into a larger one on the device between two launches
+(ScanState.grow_*); nothing is lost or read again.
 """
 
 import json
 import os
+import stat
 
 import numpy as np
 
 from ..points import Aggregator
+from . import capacity
 from . import plan as planmod
 from .chunks import _pad, choose_chunk_bytes, frame_files
 
@@ -41,6 +48,14 @@ def _env_int(name, default):
         return int(os.environ.get(name, default))
     except ValueError:
         return default
+
+
+def _is_regular(path):
+    """A path that cannot be stat'ed counts as not regular."""
+    try:
+        return stat.S_ISREG(os.stat(path).st_mode)
+    except OSError:
+        return False
 
 
 class GpuEngine(object):
@@ -79,21 +94,35 @@ class GpuEngine(object):
         dict_slots = _env_int("DRAGNET_DICT_SLOTS", 1 << 20)
         dict_data = _env_int("DRAGNET_DICT_DATA_MB", 256) * 1024 * 1024
 
-        # byte sources cannot restart, so they never risk the dense
-        # directory (its capacity bounds key cardinality)
-        dense = False if byte_source is not None else None
-        for attempt in range(4):
+        # Input that cannot be read twice cannot restart: it scans once,
+        # growable, and never risks the dense directory (its capacity
+        # bounds key cardinality).  DRAGNET_GROW=1 opts regular files in.
+        if (byte_source is not None or _env_int("DRAGNET_GROW", 0) == 1
+                or not all(_is_regular(p) for p in files)):
             ctx = _ScanContext(self, cplan, agg_slots, dict_slots,
-                               dict_data, dense=dense)
+                               dict_data, dense=False, growable=True)
             if byte_source is not None:
-                if attempt > 0:
-                    raise RuntimeError(
-                        "table overflow on non-restartable byte source")
                 for chunk in byte_source:
                     ctx.feed(chunk)
                 ctx.flush()
             else:
                 ctx.scan_files(files)
+            if ctx.overflowed():
+                # safety net (a pathological probe chain): never a
+                # partial aggregate
+                raise RuntimeError(
+                    "table overflow on non-restartable byte source")
+            aggs, stages = ctx.finalize(queries)
+            return ScanResult(aggs, stages, gpu_stats=dict(
+                ctx.planner.grow_counts(), restarts=0))
+
+        dense = None
+        nogrow = {"agg": [0] * len(queries), "sdict": 0, "sdata": 0,
+                  "ndict": 0}
+        for attempt in range(4):
+            ctx = _ScanContext(self, cplan, agg_slots, dict_slots,
+                               dict_data, dense=dense)
+            ctx.scan_files(files)
             if ctx.overflowed():
                 from ..log import get_logger
                 if ctx.dense:
@@ -113,7 +142,8 @@ class GpuEngine(object):
                 dict_data *= 4
                 continue
             aggs, stages = ctx.finalize(queries)
-            return ScanResult(aggs, stages)
+            return ScanResult(aggs, stages,
+                              gpu_stats=dict(nogrow, restarts=attempt))
         raise RuntimeError("aggregation tables overflowed after retries")
 
     def columnar_query(self, query, filt, params, kinds, cols, vals):
@@ -219,8 +249,10 @@ PROWS = 2048  # dense partial rows == the scan kernel's grid cap
 
 class _ScanContext(object):
     def __init__(self, eng, cplan, agg_slots, dict_slots, dict_data_cap,
-                 dense=None):
+                 dense=None, growable=False):
         torch = eng.torch
+        if growable:
+            dense = False  # the dense directory does not grow
         self.eng = eng
         self.t = torch
         self.cplan = cplan
@@ -317,6 +349,17 @@ class _ScanContext(object):
         self.dict_slots = dict_slots
         self._fin_stream = None  # lazy: D2H lane for pipelined decode
 
+        # Growable scans: every launch goes through the planner, which
+        # keeps the sizes from here on (agg_slots / dict_slots follow
+        # the largest table of their kind)
+        self.planner = None
+        if growable:
+            nm_, s_cols, n_cols = capacity.plan_shape(metrics, bds)
+            self.planner = capacity.CapacityPlanner(
+                nm_, s_cols, n_cols,
+                {"agg": agg_slots, "sdict": dict_slots,
+                 "sdata": dict_data_cap, "ndict": dict_slots})
+
         # Host staging state; None until the function named creates it.
         # _ensure_buffers: chunk buffers + newline index, all modes
         self._pinned = self._dev_data = None
@@ -386,7 +429,92 @@ class _ScanContext(object):
         """Newline index (unless a pre-built one is given) + fused
         scan of dev_data[start:end] on the current stream."""
         pos, nlines = index or self._index(dev_data, start, end)
-        self.state.scan(dev_data, pos, nlines, start)
+        if self.planner is None:
+            self.state.scan(dev_data, pos, nlines, start)
+        else:
+            self._scan_planned(dev_data, pos, nlines, start, end)
+
+    # ---- growable scans (engine/capacity.py) ----
+
+    def _scan_planned(self, dev_data, pos, nlines, start, end):
+        """Scan the chunk as planner-sized sub-ranges of its records,
+        growing whatever the next one might fill.  Records [a, b) are
+        launched as pos[a:b] with first_start at record a's first byte;
+        ScanState.scan clamps the device line count (the chunk's, at
+        least b - a) to that slice.  One small D2H copy — the line
+        count and the newline position ahead of every floor-th record —
+        tells the host all it plans with: a host sync per chunk, on
+        this path only."""
+        torch = self.t
+        pl = self.planner
+        g = pl.floor
+        # a chunk of end - start bytes holds at most that many lines
+        host = torch.cat(
+            [nlines, pos[g - 1:end - start:g]]).cpu().numpy()
+        nrec = min(int(host[0]), pos.numel())
+        marks = host[1:].view(np.uint32)
+
+        def start_of(i):
+            if i == 0:
+                return start
+            if i == nrec:
+                return end  # at or past the last record's newline
+            return int(marks[i // g - 1]) + 1
+
+        a = 0
+        while a < nrec:
+            b = pl.next_range(a, nrec, start_of, self._measure, self.grow)
+            self.state.scan(dev_data, pos[a:b], nlines, start_of(a))
+            a = b
+
+    def _measure(self, names):
+        """True occupancy of the named structures (one device read)."""
+        occ = self.state.occupancy().cpu().tolist()
+        true = dict(zip(self.planner.names, occ))
+        return {n: true[n] for n in names}
+
+    def grow(self, name, new_size):
+        """Grow one structure ("agg<m>", "sdict", "sdata", "ndict") to
+        new_size on the device, contents and ids preserved."""
+        torch = self.t
+        dev = self.eng.device
+        pl = self.planner
+        old = pl.size[name]
+
+        def zeros(n, dtype):
+            return torch.zeros(n, dtype=dtype, device=dev)
+
+        i32, i64 = torch.int32, torch.int64
+        try:
+            if name == "sdict":
+                self.state.grow_sdict(
+                    zeros(new_size, i32), zeros(new_size, i64),
+                    zeros(new_size, i32), zeros(new_size, i32),
+                    zeros(new_size, i32))
+            elif name == "sdata":
+                self.state.grow_sdata(zeros(new_size, torch.uint8))
+            elif name == "ndict":
+                self.state.grow_ndict(
+                    zeros(new_size, i32), zeros(new_size, i64),
+                    zeros(new_size, i32))
+            else:
+                self.state.grow_agg(
+                    int(name[3:]), zeros(new_size, i32),
+                    zeros(new_size * MAX_KEY, i32),
+                    zeros(new_size, torch.float64))
+        except torch.OutOfMemoryError as e:
+            raise RuntimeError(
+                "cannot grow %s from %d to %d: device allocation "
+                "failed (%s)" % (name, old, new_size,
+                                 str(e).splitlines()[0]))
+        pl.size[name] = new_size
+        self.agg_slots = max(pl.size[n] for n in pl.names
+                             if n.startswith("agg"))
+        self.dict_slots = max(pl.size["sdict"], pl.size["ndict"])
+        from ..log import get_logger
+        get_logger().child("gpu-engine").warn(
+            "table grown in place", structure=name, size=old,
+            new_size=new_size)
 
     def _run(self, buf):
         torch = self.t
@@ -672,6 +800,8 @@ class _ScanContext(object):
         (one binding call; ~10 separate .zero_() dispatches otherwise
         show up at 5 ms/step)."""
         self.state.reset()
+        if self.planner is not None:
+            self.planner.occ = dict.fromkeys(self.planner.names, 0)
 
     # ---- results ----
 
@@ -709,22 +839,7 @@ class _ScanContext(object):
         with torch.cuda.stream(self._fin_stream):
             self._fin_stream.wait_event(h["ev"])
             cnt = h["cnt"].cpu().numpy()
-
-            # dictionaries
-            n_str = int(h["n_str"].item())
-            n_num = int(h["n_num"].item())
-            strings = []
-            if n_str:
-                off = h["str_off"][:n_str].cpu().numpy().astype(np.uint32)
-                ln = h["str_len"][:n_str].cpu().numpy().astype(np.uint32)
-                used = int(h["used"].item())
-                blob = h["blob"][:used].cpu().numpy().tobytes()
-                for i in range(n_str):
-                    raw = blob[off[i]:off[i] + ln[i]]
-                    strings.append(_decode_json_string(raw))
-            numbers = np.zeros(0)
-            if n_num:
-                numbers = h["numbers"][:n_num].cpu().numpy()
+            strings, numbers = self._decode_dicts(h)
             hostk = []
             for m, _q in enumerate(queries):
                 k_full, c_full, out_n = h["aggs"][m]
@@ -754,6 +869,26 @@ class _ScanContext(object):
             if name == "Aggregator":
                 c["noutputs"] = aggs[0].noutputs()
         return aggs, stages
+
+    @staticmethod
+    def _decode_dicts(h):
+        """The extraction's dictionaries in id order: (strings list,
+        numbers array).  The caller has waited for h["ev"]."""
+        n_str = int(h["n_str"].item())
+        n_num = int(h["n_num"].item())
+        strings = []
+        if n_str:
+            off = h["str_off"][:n_str].cpu().numpy().astype(np.uint32)
+            ln = h["str_len"][:n_str].cpu().numpy().astype(np.uint32)
+            used = int(h["used"].item())
+            blob = h["blob"][:used].cpu().numpy().tobytes()
+            for i in range(n_str):
+                raw = blob[off[i]:off[i] + ln[i]]
+                strings.append(_decode_json_string(raw))
+        numbers = np.zeros(0)
+        if n_num:
+            numbers = h["numbers"][:n_num].cpu().numpy()
+        return strings, numbers
 
     def _counter_stages(self, cnt, queries):
         """Reconstruct the reference pipeline counter stages from the

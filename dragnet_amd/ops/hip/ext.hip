@@ -210,64 +210,35 @@ class ScanState {
         (uint64_t)py::cast<int64_t>(plan["fields_parent_sig"]);
     args_.data_format_skinner = py::cast<bool>(plan["skinner"]) ? 1 : 0;
 
-    // named members (reset / extract_all use the tensors themselves)
-    sd_state_ = tensor_at(sdict, "state");
-    sd_data_ = tensor_at(sdict, "data");
+    // dictionaries: every tensor is a named member (reset, extract_all
+    // and grow_* use the tensors themselves)
     sd_used_ = tensor_at(sdict, "used");
     sd_next_ = tensor_at(sdict, "next");
-    sd.state = (uint32_t*)sd_state_.data_ptr();
-    sd.hash = (uint64_t*)ptr(sdict, "hash");
-    sd.id = (uint32_t*)ptr(sdict, "id");
-    sd.off = (uint32_t*)ptr(sdict, "off");
-    sd.len = (uint32_t*)ptr(sdict, "len");
-    sd.nslots = (uint32_t)sd_state_.numel();
-    sd.data = (uint8_t*)sd_data_.data_ptr();
-    sd.data_cap = (uint32_t)sd_data_.numel();
+    CHECK_GPU(sd_used_);
+    CHECK_GPU(sd_next_);
     sd.data_used = (uint32_t*)sd_used_.data_ptr();
     sd.next_id = (uint32_t*)sd_next_.data_ptr();
+    bind_sdict_slots(tensor_at(sdict, "state"), tensor_at(sdict, "hash"),
+                     tensor_at(sdict, "id"), tensor_at(sdict, "off"),
+                     tensor_at(sdict, "len"));
+    bind_sdict_data(tensor_at(sdict, "data"));
 
-    nd_state_ = tensor_at(ndict, "state");
     nd_next_ = tensor_at(ndict, "next");
-    nd.state = (uint32_t*)nd_state_.data_ptr();
-    nd.bits = (uint64_t*)ptr(ndict, "bits");
-    nd.id = (uint32_t*)ptr(ndict, "id");
-    nd.nslots = (uint32_t)nd_state_.numel();
+    CHECK_GPU(nd_next_);
     nd.next_id = (uint32_t*)nd_next_.data_ptr();
+    bind_ndict_slots(tensor_at(ndict, "state"), tensor_at(ndict, "bits"),
+                     tensor_at(ndict, "id"));
 
-    // per-metric table descriptors, uploaded once
+    // per-metric table descriptors
     size_t nm = states_.size();
     TORCH_CHECK((int)nm == P.nm && keys_.size() == nm &&
                     counts_.size() == nm &&
                     (partials_.empty() || partials_.size() == nm),
                 "one table (and partial) per metric");
-    tables_.resize(nm);
-    for (size_t m = 0; m < nm; m++) {
-      AggTable& t = tables_[m];
-      t.state = (uint32_t*)states_[m].data_ptr();
-      t.keys = (uint32_t*)keys_[m].data_ptr();
-      t.count = (double*)counts_[m].data_ptr();
-      t.nslots = (uint32_t)states_[m].numel();
-      t.partial = nullptr;
-      t.prows = 0;
-      t.pad_ = 0;
-      if (!partials_.empty()) {
-        TORCH_CHECK(partials_[m].size(1) == (long)t.nslots,
-                    "partial width != nslots");
-        t.partial = (double*)partials_[m].data_ptr();
-        t.prows = (uint32_t)partials_[m].size(0);
-      }
-    }
-    // every descriptor above holds a raw device pointer
-    for (auto* group : {&states_, &keys_, &counts_, &partials_, &owned_})
+    // every plan descriptor holds a raw device pointer
+    for (auto* group : {&partials_, &owned_})
       for (auto& t : *group) CHECK_GPU(t);
-    for (auto* t : {&sd_state_, &sd_data_, &sd_used_, &sd_next_,
-                    &nd_state_, &nd_next_})
-      CHECK_GPU(*t);
-    auto host = torch::empty({(long)(nm * sizeof(AggTable))},
-                             torch::dtype(torch::kUInt8));
-    memcpy(host.data_ptr(), tables_.data(), nm * sizeof(AggTable));
-    table_descs_ = host.to(counters_.device());
-    args_.tables = (AggTable*)table_descs_.data_ptr();
+    bind_tables();
     args_.counters = (unsigned long long*)counters_.data_ptr();
 
     // experiment knobs: read once, here — never per launch.  Default 4
@@ -437,7 +408,184 @@ class ScanState {
     return out;
   }
 
+  // ---- in-place growth (hash path only; engine/capacity.py plans it) ----
+  // Each grow_* takes freshly ZEROED tensors of the new size, enqueues
+  // the rehash (scan_rehash.h) on the current stream and rebinds the
+  // descriptors; the old tensors stay referenced until that launch is
+  // enqueued and are then dropped (the allocator reuses them in stream
+  // order).  lds_, the launch knobs and the counters are unaffected: a
+  // placement that cannot be made bumps C_OVERFLOW, nothing else does.
+
+  // Current occupancy of every growable structure, on device, no sync:
+  // int64 [ready slots per metric..., string ids, payload bytes used,
+  // number ids].
+  torch::Tensor occupancy() {
+    std::vector<torch::Tensor> parts;
+    for (auto& st : states_)
+      parts.push_back(st.eq((int64_t)SLOT_READY).sum().reshape({1}));
+    for (auto* t : {&sd_next_, &sd_used_, &nd_next_})
+      parts.push_back(t->to(torch::kInt64));
+    return torch::cat(parts);
+  }
+
+  void grow_agg(int64_t m, torch::Tensor state, torch::Tensor keys,
+                torch::Tensor count) {
+    TORCH_CHECK(partials_.empty(), "dense tables do not grow");
+    TORCH_CHECK(m >= 0 && (size_t)m < tables_.size(), "no such metric");
+    AggTable old = tables_[m];
+    check_growth(old.nslots, checked_slots(state, "agg table"));
+    std::vector<torch::Tensor> keep = {states_[m], keys_[m], counts_[m]};
+    states_[m] = std::move(state);
+    keys_[m] = std::move(keys);
+    counts_[m] = std::move(count);
+    bind_tables();
+    launch("rehash_agg", rehash_agg_kernel, dim3((old.nslots + 255) / 256),
+           dim3(256), 0, old, tables_[m], overflow_ptr());
+  }
+
+  void grow_sdict(torch::Tensor state, torch::Tensor hash,
+                  torch::Tensor id, torch::Tensor off, torch::Tensor len) {
+    StrDict old = args_.sdict;
+    check_growth(old.nslots, checked_slots(state, "sdict"));
+    std::vector<torch::Tensor> keep = {sd_state_, sd_hash_, sd_id_,
+                                       sd_off_, sd_len_};
+    bind_sdict_slots(std::move(state), std::move(hash), std::move(id),
+                     std::move(off), std::move(len));
+    launch("rehash_strdict", rehash_strdict_kernel,
+           dim3((old.nslots + 255) / 256), dim3(256), 0, old, args_.sdict,
+           overflow_ptr());
+  }
+
+  // The payload blob moves to the same offsets: a plain device copy.
+  void grow_sdata(torch::Tensor data) {
+    torch::Tensor old = sd_data_;
+    TORCH_CHECK(data.numel() > old.numel(),
+                "string payload buffer may only grow");
+    bind_sdict_data(std::move(data));
+    hipError_t e = hipMemcpyAsync(sd_data_.data_ptr(), old.data_ptr(),
+                                  (size_t)old.numel(),
+                                  hipMemcpyDeviceToDevice,
+                                  current_stream());
+    TORCH_CHECK(e == hipSuccess, "payload copy failed: ",
+                hipGetErrorString(e));
+  }
+
+  void grow_ndict(torch::Tensor state, torch::Tensor bits,
+                  torch::Tensor id) {
+    NumDict old = args_.ndict;
+    check_growth(old.nslots, checked_slots(state, "ndict"));
+    std::vector<torch::Tensor> keep = {nd_state_, nd_bits_, nd_id_};
+    bind_ndict_slots(std::move(state), std::move(bits), std::move(id));
+    launch("rehash_numdict", rehash_numdict_kernel,
+           dim3((old.nslots + 255) / 256), dim3(256), 0, old, args_.ndict,
+           overflow_ptr());
+  }
+
  private:
+  // A descriptor array over `n` elements of `dtype` on the GPU.
+  static void* checked_ptr(const torch::Tensor& t, int64_t n,
+                           torch::ScalarType dtype, const char* what) {
+    TORCH_CHECK(t.is_cuda() && t.is_contiguous() &&
+                    t.scalar_type() == dtype && t.numel() == n,
+                what, ": need a contiguous GPU tensor of ", n,
+                " elements");
+    return t.data_ptr();
+  }
+
+  // slot counts are masks (power of two) and uint32 on the device
+  static uint32_t checked_slots(const torch::Tensor& state,
+                                const char* what) {
+    int64_t n = state.numel();
+    TORCH_CHECK(n > 0 && (n & (n - 1)) == 0 && n <= ((int64_t)1 << 31),
+                what, ": slot count must be a power of two <= 2^31");
+    return (uint32_t)n;
+  }
+
+  static void check_growth(uint32_t old_slots, uint32_t new_slots) {
+    TORCH_CHECK(new_slots > old_slots, "a table may only grow (", old_slots,
+                " -> ", new_slots, " slots)");
+  }
+
+  unsigned long long* overflow_ptr() {
+    return (unsigned long long*)counters_.data_ptr() + C_OVERFLOW;
+  }
+
+  void bind_sdict_slots(torch::Tensor state, torch::Tensor hash,
+                        torch::Tensor id, torch::Tensor off,
+                        torch::Tensor len) {
+    StrDict& sd = args_.sdict;
+    int64_t n = checked_slots(state, "sdict");
+    sd.state = (uint32_t*)checked_ptr(state, n, torch::kInt32, "sdict.state");
+    sd.hash = (uint64_t*)checked_ptr(hash, n, torch::kInt64, "sdict.hash");
+    sd.id = (uint32_t*)checked_ptr(id, n, torch::kInt32, "sdict.id");
+    sd.off = (uint32_t*)checked_ptr(off, n, torch::kInt32, "sdict.off");
+    sd.len = (uint32_t*)checked_ptr(len, n, torch::kInt32, "sdict.len");
+    sd.nslots = (uint32_t)n;
+    sd_state_ = std::move(state);
+    sd_hash_ = std::move(hash);
+    sd_id_ = std::move(id);
+    sd_off_ = std::move(off);
+    sd_len_ = std::move(len);
+  }
+
+  void bind_sdict_data(torch::Tensor data) {
+    // offsets into the payload are uint32
+    TORCH_CHECK(data.numel() <= (int64_t)0xFFFFFFFFll,
+                "string payload buffer exceeds 32-bit offsets");
+    args_.sdict.data = (uint8_t*)checked_ptr(data, data.numel(),
+                                             torch::kUInt8, "sdict.data");
+    args_.sdict.data_cap = (uint32_t)data.numel();
+    sd_data_ = std::move(data);
+  }
+
+  void bind_ndict_slots(torch::Tensor state, torch::Tensor bits,
+                        torch::Tensor id) {
+    NumDict& nd = args_.ndict;
+    int64_t n = checked_slots(state, "ndict");
+    nd.state = (uint32_t*)checked_ptr(state, n, torch::kInt32, "ndict.state");
+    nd.bits = (uint64_t*)checked_ptr(bits, n, torch::kInt64, "ndict.bits");
+    nd.id = (uint32_t*)checked_ptr(id, n, torch::kInt32, "ndict.id");
+    nd.nslots = (uint32_t)n;
+    nd_state_ = std::move(state);
+    nd_bits_ = std::move(bits);
+    nd_id_ = std::move(id);
+  }
+
+  // (Re)build the per-metric table descriptors from states_/keys_/
+  // counts_/partials_ and upload them.  keys are indexed slot * MAX_KEY
+  // in uint32 on the device.
+  void bind_tables() {
+    size_t nm = states_.size();
+    tables_.resize(nm);
+    for (size_t m = 0; m < nm; m++) {
+      AggTable& t = tables_[m];
+      int64_t n = checked_slots(states_[m], "agg table");
+      TORCH_CHECK(n <= ((int64_t)1 << 29),
+                  "agg table: slot * MAX_KEY must fit uint32");
+      t.state = (uint32_t*)checked_ptr(states_[m], n, torch::kInt32,
+                                       "agg state");
+      t.keys = (uint32_t*)checked_ptr(keys_[m], n * MAX_KEY, torch::kInt32,
+                                      "agg keys");
+      t.count = (double*)checked_ptr(counts_[m], n, torch::kFloat64,
+                                     "agg count");
+      t.nslots = (uint32_t)n;
+      t.partial = nullptr;
+      t.prows = 0;
+      t.pad_ = 0;
+      if (!partials_.empty()) {
+        TORCH_CHECK(partials_[m].size(1) == (long)t.nslots,
+                    "partial width != nslots");
+        t.partial = (double*)partials_[m].data_ptr();
+        t.prows = (uint32_t)partials_[m].size(0);
+      }
+    }
+    auto host = torch::empty({(long)(nm * sizeof(AggTable))},
+                             torch::dtype(torch::kUInt8));
+    memcpy(host.data_ptr(), tables_.data(), nm * sizeof(AggTable));
+    table_descs_ = host.to(counters_.device());
+    args_.tables = (AggTable*)table_descs_.data_ptr();
+  }
+
   // Fold a dense partial matrix into count[] with the MFMA column-sum
   // reduce (must run before extraction of a dense-mode table).
   static void dense_reduce(const AggTable& T) {
@@ -451,12 +599,14 @@ class ScanState {
            dim3(64), 0, T, rows_per_blk);
   }
 
-  // owned tensors: named where a method needs the tensor itself,
-  // owned_ for those only the descriptors point at
+  // owned tensors: named where a method needs the tensor itself (or
+  // growth replaces it), owned_ for the plan's, which only the
+  // descriptors point at
   std::vector<torch::Tensor> states_, keys_, counts_, partials_, owned_;
   std::vector<torch::Tensor> col_inputs_;  // last columnar_query's inputs
-  torch::Tensor sd_state_, sd_data_, sd_used_, sd_next_;
-  torch::Tensor nd_state_, nd_next_;
+  torch::Tensor sd_state_, sd_hash_, sd_id_, sd_off_, sd_len_;
+  torch::Tensor sd_data_, sd_used_, sd_next_;
+  torch::Tensor nd_state_, nd_bits_, nd_id_, nd_next_;
   torch::Tensor counters_, table_descs_;
   // prebuilt launch arguments: the PlanView, StrDict and NumDict, the
   // table/counter pointers and the tile size; a launch copies them and
@@ -496,7 +646,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::arg("nrows"), py::arg("columns"),
            "K7: query over uploaded index columns")
       .def("reset", &dn::ScanState::reset)
-      .def("extract_all", &dn::ScanState::extract_all);
+      .def("extract_all", &dn::ScanState::extract_all)
+      .def("occupancy", &dn::ScanState::occupancy,
+           "device int64 [ready slots per metric..., string ids, "
+           "payload bytes, number ids]")
+      .def("grow_agg", &dn::ScanState::grow_agg, py::arg("metric"),
+           py::arg("state"), py::arg("keys"), py::arg("count"),
+           "rehash one metric's table into larger zeroed tensors")
+      .def("grow_sdict", &dn::ScanState::grow_sdict, py::arg("state"),
+           py::arg("hash"), py::arg("id"), py::arg("off"), py::arg("len"))
+      .def("grow_sdata", &dn::ScanState::grow_sdata, py::arg("data"))
+      .def("grow_ndict", &dn::ScanState::grow_ndict, py::arg("state"),
+           py::arg("bits"), py::arg("id"));
   m.attr("MAX_KEY") = (int)dn::MAX_KEY;
   m.attr("MAX_FIELDS") = (int)dn::MAX_FIELDS;
 }

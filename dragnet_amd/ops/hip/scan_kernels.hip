@@ -16,7 +16,8 @@
 // fences (L1 invalidates) appear on the hot path.
 //
 // Layers (docs/DESIGN.md): scan_text.h, scan_record.h (record semantics,
-// host-compilable too), scan_tables.h (device only), the kernels here.
+// host-compilable too), scan_tables.h (device only), the kernels here,
+// scan_rehash.h (device only: table growth between launches).
 
 #include "common.h"
 #include <hip/hip_runtime.h>
@@ -694,5 +695,9 @@ __global__ void extract_numdict_kernel(NumDict D, double* out_vals,
 }
 
 }  // namespace dn
+
+// in-place table growth (the rehash kernels); last, so the kernels
+// above keep their place in the module
+#include "scan_rehash.h"
 
 }  // extern "C++"

@@ -83,10 +83,15 @@ DEV uint32_t intern_string(const StrDict& D, BS BV,
   return 0xFFFFFFFFu;
 }
 
+// Home-slot hash of a number-dictionary entry (canonical double bits).
+DEV uint64_t number_hash(uint64_t bits) {
+  return mix64(bits ^ 0x9E3779B97F4A7C15ull);
+}
+
 DEV uint32_t intern_number(const NumDict& D, double v) {
   if (v == 0.0) v = 0.0;  // canonicalize -0
   uint64_t bits = __double_as_longlong(v);
-  uint64_t h = mix64(bits ^ 0x9E3779B97F4A7C15ull);
+  uint64_t h = number_hash(bits);
   uint32_t mask = D.nslots - 1;
   uint32_t s = (uint32_t)h & mask;
   for (uint32_t probes = 0; probes < D.nslots; probes++, s = (s + 1) & mask) {
@@ -117,14 +122,25 @@ DEV uint32_t intern_number(const NumDict& D, double v) {
 // -------------------------------------------------------------------
 // global aggregation insert (K5)
 
-DEV bool agg_insert(const AggTable& T, const uint32_t* key, int nk,
-                    double w) {
+// Home-slot hash of a group key: columns past nk hash as 0, which is
+// also how they are stored, so hashing a stored key with nk = MAX_KEY
+// (the table rehash, scan_rehash.h) gives the inserting scan's value.
+DEV uint64_t agg_table_hash(const uint32_t* key, int nk) {
   uint64_t h = FNV_OFFSET;
   for (int k = 0; k < MAX_KEY; k++)
     h = mix64(h ^ (k < nk ? key[k] : 0u) ^ (uint64_t)(k + 1) * 0x9E3779B97F4A7C15ull);
+  return h;
+}
+
+// agg_insert gives up after this many probes (C_OVERFLOW)
+constexpr uint32_t AGG_MAX_PROBES = 4096u;
+
+DEV bool agg_insert(const AggTable& T, const uint32_t* key, int nk,
+                    double w) {
+  uint64_t h = agg_table_hash(key, nk);
   uint32_t mask = T.nslots - 1;
   uint32_t s = (uint32_t)h & mask;
-  for (uint32_t probes = 0; probes < 4096u; probes++, s = (s + 1) & mask) {
+  for (uint32_t probes = 0; probes < AGG_MAX_PROBES; probes++, s = (s + 1) & mask) {
     while (true) {
       uint32_t st = atomic_load_relaxed(&T.state[s]);
       if (st == SLOT_READY) {
@@ -163,9 +179,7 @@ DEV bool agg_insert(const AggTable& T, const uint32_t* key, int nk,
 // MFMA reduce.  Returns the slot index or ~0u on probe exhaustion.
 DEV uint32_t agg_insert_slot(const AggTable& T, const uint32_t* key,
                              int nk) {
-  uint64_t h = FNV_OFFSET;
-  for (int k = 0; k < MAX_KEY; k++)
-    h = mix64(h ^ (k < nk ? key[k] : 0u) ^ (uint64_t)(k + 1) * 0x9E3779B97F4A7C15ull);
+  uint64_t h = agg_table_hash(key, nk);
   uint32_t mask = T.nslots - 1;
   uint32_t s = (uint32_t)h & mask;
   // TIGHT probe cap: once the directory saturates, every further
