@@ -5,10 +5,12 @@ Streams NDJSON bytes through the fused CDNA4 scan kernel
 (ops/hip/scan_kernels.hip): chunked reads into pinned host buffers,
 async H2D on the current HIP stream, torch-side newline indexing, one
 fused kernel launch per chunk, then table/dictionary extraction and
-host-side decode into the same canonical aggregate representation the
-CPU oracle produces (points.Aggregator) — so every downstream consumer
-(formatters, index sink, RCCL merge) is engine-agnostic.  File scans
-take their chunks from the host-only framer in engine/chunks.py.
+host-side decode (engine/decode.py) into the same canonical aggregate
+representation the CPU oracle produces (points.Aggregator) — so every
+downstream consumer (formatters, index sink, RCCL merge) is
+engine-agnostic.  File scans take their chunks from the host-only
+framer in engine/chunks.py.  The tables, dictionaries and counters
+belong to the extension's ScanState, which allocates and grows them.
 
 Capacity handling: the hash tables and dictionaries are sized up front,
 as a first guess.  A scan of regular files restarts on overflow
@@ -21,26 +23,20 @@ fill is rehashed into a larger one on the device between two launches
 (ScanState.grow_*); nothing is lost or read again.
 """
 
-import json
 import os
 import stat
+from types import SimpleNamespace
 
 import numpy as np
 
-from ..points import Aggregator
-from . import capacity
+from . import capacity, decode, xpose
 from . import plan as planmod
 from .chunks import _pad, choose_chunk_bytes, frame_files
-
-# device counter slots (ops/hip/common.h CounterSlot)
-(C_LINES, C_INVALID_JSON, C_PARSED, C_DS_FILTERED, C_DS_FAILEDEVAL,
- C_OVERFLOW) = range(6)
-C_GLOBAL_N = 8
-CM_N = 8
-(CM_FILTER_IN, CM_FILTERED, CM_FAILEDEVAL, CM_UNDEF, CM_BADDATE,
- CM_TIME_OUT, CM_AGG_IN, CM_NONNUMERIC) = range(8)
-
-MAX_KEY = 8
+from .decode import (  # noqa: F401  (the counter slots, for importers)
+    C_DS_FAILEDEVAL, C_DS_FILTERED, C_GLOBAL_N, C_INVALID_JSON, C_LINES,
+    C_OVERFLOW, C_PARSED, CM_AGG_IN, CM_BADDATE, CM_FAILEDEVAL,
+    CM_FILTER_IN, CM_FILTERED, CM_N, CM_NONNUMERIC, CM_TIME_OUT, CM_UNDEF)
+from .xpose import _build_xpose_layout  # noqa: F401  (its earlier home)
 
 
 def _env_int(name, default):
@@ -244,9 +240,6 @@ class GpuEngine(object):
         raise RuntimeError("columnar query overflowed after retry")
 
 
-PROWS = 2048  # dense partial rows == the scan kernel's grid cap
-
-
 class _ScanContext(object):
     def __init__(self, eng, cplan, agg_slots, dict_slots, dict_data_cap,
                  dense=None, growable=False):
@@ -259,18 +252,15 @@ class _ScanContext(object):
         dev = eng.device
         # Dense-accumulation mode (default on): the aggregate table is
         # a small slot directory, per-workgroup counts go to a dense
-        # [PROWS, slots] partial matrix, and the MFMA f64 column-sum
-        # reduce folds it before extraction.  High
-        # cardinality overflows the directory and the engine restarts
-        # with dense off (the atomic hash path).
+        # partial matrix, and the MFMA f64 column-sum reduce folds it
+        # before extraction.  High cardinality overflows
+        # the directory and the engine restarts with dense off (the
+        # atomic hash path).
         if dense is None:
             dense = _env_int("DRAGNET_DENSE", 1) == 1
         self.dense = dense
         if dense:
             agg_slots = _env_int("DRAGNET_DENSE_SLOTS", 8192)
-        i32 = dict(dtype=torch.int32, device=dev)
-        f64 = dict(dtype=torch.float64, device=dev)
-        u8 = dict(dtype=torch.uint8, device=dev)
 
         def dev_i32(np_arr):
             return torch.from_numpy(
@@ -307,77 +297,51 @@ class _ScanContext(object):
             fields_slot=cplan.fields_slot,
             skinner=cplan.data_format == "json-skinner",
         )
-        nm = metrics.shape[0]
 
-        # per-metric tables (+ dense partial matrices)
-        states = [torch.zeros(agg_slots, **i32) for _ in range(nm)]
-        keys = [torch.zeros(agg_slots * MAX_KEY, **i32)
-                for _ in range(nm)]
-        counts = [torch.zeros(agg_slots, **f64) for _ in range(nm)]
-        partials = [torch.zeros((PROWS, agg_slots), **f64)
-                    for _ in range(nm)] if dense else []
-
-        # dictionaries
-        sdict = dict(
-            state=torch.zeros(dict_slots, **i32),
-            hash=torch.zeros(dict_slots, dtype=torch.int64, device=dev),
-            id=torch.zeros(dict_slots, **i32),
-            off=torch.zeros(dict_slots, **i32),
-            len=torch.zeros(dict_slots, **i32),
-            data=torch.zeros(dict_data_cap, **u8),
-            used=torch.zeros(1, **i32),
-            next=torch.zeros(1, **i32),
-        )
-        ndict = dict(
-            state=torch.zeros(dict_slots, **i32),
-            bits=torch.zeros(dict_slots, dtype=torch.int64, device=dev),
-            id=torch.zeros(dict_slots, **i32),
-            next=torch.zeros(1, **i32),
-        )
-        self.counters = torch.zeros(
-            C_GLOBAL_N + nm * CM_N, dtype=torch.int64, device=dev)
-
-        # The bound extension object owns all of the above (the kernel
-        # descriptors point into these tensors) and caches the launch
-        # knobs (DRAGNET_MIN_WAVES / XGRAN / LDS_STAGE) as of now.
+        # The bound extension object allocates and owns the tables,
+        # dictionaries and counters (the kernel descriptors point into
+        # its tensors) and caches the launch knobs (DRAGNET_MIN_WAVES /
+        # XGRAN / LDS_STAGE) as of now.
         self.state = eng.ops.ScanState(
-            plan=plan, states=states, keys=keys, counts=counts,
-            partials=partials, sdict=sdict, ndict=ndict,
-            counters=self.counters)
-
-        self.agg_slots = agg_slots
-        self.dict_slots = dict_slots
-        self._fin_stream = None  # lazy: D2H lane for pipelined decode
+            plan=plan, agg_slots=agg_slots, dict_slots=dict_slots,
+            dict_data_bytes=dict_data_cap, dense=dense)
 
         # Growable scans: every launch goes through the planner, which
-        # keeps the sizes from here on (agg_slots / dict_slots follow
-        # the largest table of their kind)
+        # books occupancy against the state's sizes
         self.planner = None
         if growable:
-            nm_, s_cols, n_cols = capacity.plan_shape(metrics, bds)
+            nm, s_cols, n_cols = capacity.plan_shape(metrics, bds)
+            sizes = self.state.sizes()
             self.planner = capacity.CapacityPlanner(
-                nm_, s_cols, n_cols,
-                {"agg": agg_slots, "sdict": dict_slots,
-                 "sdata": dict_data_cap, "ndict": dict_slots})
+                nm, s_cols, n_cols,
+                dict(sizes, agg=[sizes["agg%d" % m] for m in range(nm)]))
 
-        # Host staging state; None until the function named creates it.
-        # _ensure_buffers: chunk buffers + newline index, all modes
+        # chunk buffers + newline index, all modes (_ensure_buffers)
         self._pinned = self._dev_data = None
         self._pos = self._nlines = self._segs = None
         # feed/flush: the one pinned buffer, copies on the current stream
         self._partial = b""
         self._copy_ev = None  # guards pinned-buffer reuse across chunks
-        # _ensure_file_staging: ping-pong buffers + copy stream
-        self._fs_pins = self._fs_dev = self._fs_done = None
-        self._fs_copy_stream = None
-        self._fs_idx = 0
-        # stage_resident: slices, slice events, pass ping-pong
-        self._resident = None  # (n, padded)
-        self._slices = self._slice_evs = self._slice_pos = None
-        self._copy_stream = self._dev_data_pp = self._pass_done = None
-        self._db_idx = 0
-        # stage_xpose: (xdata, wave_base, rec_len, n_slots)
-        self._x = None
+        self._fin_stream = None  # lazy: D2H lane for pipelined decode
+        # staging state of one mode each, created by the method named:
+        self._files = None  # _ensure_file_staging: ping-pong buffers
+        self._pool = None   # stage_resident: slices + pass ping-pong
+        self._x = None      # stage_xpose: ScanState.scan_xpose's arguments
+
+    @property
+    def counters(self):
+        return self.state.counters
+
+    @property
+    def agg_slots(self):
+        """Slots of the largest aggregation table."""
+        return max(v for k, v in self.state.sizes().items()
+                   if k.startswith("agg"))
+
+    @property
+    def dict_slots(self):
+        sizes = self.state.sizes()
+        return max(sizes["sdict"], sizes["ndict"])
 
     # ---- chunk feeding ----
 
@@ -476,41 +440,12 @@ class _ScanContext(object):
     def grow(self, name, new_size):
         """Grow one structure ("agg<m>", "sdict", "sdata", "ndict") to
         new_size on the device, contents and ids preserved."""
-        torch = self.t
-        dev = self.eng.device
-        pl = self.planner
-        old = pl.size[name]
-
-        def zeros(n, dtype):
-            return torch.zeros(n, dtype=dtype, device=dev)
-
-        i32, i64 = torch.int32, torch.int64
-        try:
-            if name == "sdict":
-                self.state.grow_sdict(
-                    zeros(new_size, i32), zeros(new_size, i64),
-                    zeros(new_size, i32), zeros(new_size, i32),
-                    zeros(new_size, i32))
-            elif name == "sdata":
-                self.state.grow_sdata(zeros(new_size, torch.uint8))
-            elif name == "ndict":
-                self.state.grow_ndict(
-                    zeros(new_size, i32), zeros(new_size, i64),
-                    zeros(new_size, i32))
-            else:
-                self.state.grow_agg(
-                    int(name[3:]), zeros(new_size, i32),
-                    zeros(new_size * MAX_KEY, i32),
-                    zeros(new_size, torch.float64))
-        except torch.OutOfMemoryError as e:
-            raise RuntimeError(
-                "cannot grow %s from %d to %d: device allocation "
-                "failed (%s)" % (name, old, new_size,
-                                 str(e).splitlines()[0]))
-        pl.size[name] = new_size
-        self.agg_slots = max(pl.size[n] for n in pl.names
-                             if n.startswith("agg"))
-        self.dict_slots = max(pl.size["sdict"], pl.size["ndict"])
+        old = self.planner.size[name]
+        if name.startswith("agg"):
+            self.state.grow_agg(int(name[3:]), new_size)
+        else:
+            getattr(self.state, "grow_" + name)(new_size)
+        self.planner.size[name] = new_size
         from ..log import get_logger
         get_logger().child("gpu-engine").warn(
             "table grown in place", structure=name, size=old,
@@ -575,38 +510,40 @@ class _ScanContext(object):
         instead of their sum (serial: 12-15 GB/s end-to-end vs the
         67 GB/s the readers deliver; profiles/r02).  Returns the pins."""
         torch = self.t
-        if self._fs_pins is None:
+        if self._files is None:
             if self._pinned is None:
                 self._ensure_buffers(_pad(cap))
-            self._fs_pins = [self._pinned, torch.empty(
-                self._pinned.numel(), dtype=torch.uint8, pin_memory=True)]
-            self._fs_copy_stream = torch.cuda.Stream(
-                device=self.eng.device)
-            self._fs_dev = [self._dev_data,
-                            torch.empty_like(self._dev_data)]
-            self._fs_done = [torch.cuda.Event(), torch.cuda.Event()]
-        return self._fs_pins
+            self._files = SimpleNamespace(
+                pins=[self._pinned, torch.empty(
+                    self._pinned.numel(), dtype=torch.uint8,
+                    pin_memory=True)],
+                copy_stream=torch.cuda.Stream(device=self.eng.device),
+                dev=[self._dev_data, torch.empty_like(self._dev_data)],
+                done=[torch.cuda.Event(), torch.cuda.Event()],
+                idx=0)
+        return self._files.pins
 
     def _run_pinned(self, pin, n):
         """H2D + kernels for pin[:n] (already newline-terminated).
         Returns the H2D-complete event — the caller must wait on it
         before refilling this pinned buffer."""
         torch = self.t
+        f = self._files
         padded = self._pad_pinned(pin, n)
-        idx = self._fs_idx
-        self._fs_idx ^= 1
-        dev_data = self._fs_dev[idx]
+        idx = f.idx
+        f.idx ^= 1
+        dev_data = f.dev[idx]
         main = torch.cuda.current_stream(self.eng.device)
-        cs = self._fs_copy_stream
+        cs = f.copy_stream
         # last kernel reader of this device buffer must finish first
-        cs.wait_event(self._fs_done[idx])
+        cs.wait_event(f.done[idx])
         ev = torch.cuda.Event()
         with torch.cuda.stream(cs):
             dev_data[:padded].copy_(pin[:padded], non_blocking=True)
             ev.record(cs)
         main.wait_event(ev)
         self._submit(dev_data, 0, n)
-        self._fs_done[idx].record(main)
+        f.done[idx].record(main)
         return ev
 
     # ---- resident-pool path (bench / repeated scans) ----
@@ -629,27 +566,27 @@ class _ScanContext(object):
         # newline-aligned slice boundaries
         bounds = sorted({0, n} | {buf.rfind(b"\n", 0, n * k // n_slices) + 1
                                   for k in range(1, n_slices)})
-        self._slices = list(zip(bounds, bounds[1:]))
-        self._resident = (n, padded)
-        self._copy_stream = torch.cuda.Stream(device=self.eng.device)
-        self._slice_evs = [torch.cuda.Event() for _ in self._slices]
+        slices = list(zip(bounds, bounds[1:]))
         # Ping-pong device pools for streaming passes: pass k+1's H2D
         # lands in the buffer pass k is NOT reading, so the copy
         # stream runs back-to-back at link rate instead of stalling
         # behind pass k's kernel tail + extraction + reset.
-        self._dev_data_pp = torch.empty_like(self._dev_data)
-        self._pass_done = [torch.cuda.Event(), torch.cuda.Event()]
-        self._db_idx = 0
+        self._pool = p = SimpleNamespace(
+            n=n, padded=padded, slices=slices,
+            copy_stream=torch.cuda.Stream(device=self.eng.device),
+            evs=[torch.cuda.Event() for _ in slices],
+            dev_pp=torch.empty_like(self._dev_data),
+            pass_done=[torch.cuda.Event(), torch.cuda.Event()],
+            idx=0, pos=[])
 
         # Pre-index line positions per slice: the pool bytes are
         # identical on every pass, so the line index is computed once
         # here (a re-scanning engine retains its line index the same
         # way the reference retains its on-disk indexes).
         self._dev_data[:padded].copy_(pin[:padded])
-        self._slice_pos = []
-        for (s, e) in self._slices:
+        for (s, e) in slices:
             pos, nlines = self._index(self._dev_data, s, e)
-            self._slice_pos.append(
+            p.pos.append(
                 (pos[:int(nlines.item())].clone(), nlines.clone()))
 
     def scan_resident(self, h2d=True):
@@ -658,7 +595,8 @@ class _ScanContext(object):
         the compute stream.  h2d=False skips the copies (device-
         resident re-scan: data already in HBM from a previous pass)."""
         torch = self.t
-        n, padded = self._resident
+        p = self._pool
+        padded = p.padded
         dev_data = self._dev_data
         pin = self._pinned
         main = torch.cuda.current_stream(self.eng.device)
@@ -667,103 +605,55 @@ class _ScanContext(object):
             # read; wait only for the pass-before-last (the last
             # reader of this buffer), which has long finished — so
             # the copies chain back-to-back across passes
-            idx = self._db_idx
-            self._db_idx ^= 1
-            dev_data = self._dev_data if idx == 0 else self._dev_data_pp
-            ev_done = self._pass_done[idx]
-            self._copy_stream.wait_event(ev_done)
-            with torch.cuda.stream(self._copy_stream):
-                for k, (s, e) in enumerate(self._slices):
+            idx = p.idx
+            p.idx ^= 1
+            dev_data = self._dev_data if idx == 0 else p.dev_pp
+            ev_done = p.pass_done[idx]
+            p.copy_stream.wait_event(ev_done)
+            with torch.cuda.stream(p.copy_stream):
+                for k, (s, e) in enumerate(p.slices):
                     s16 = s & ~15
                     e16 = min((e + 15) & ~15, padded)
                     dev_data[s16:e16].copy_(pin[s16:e16],
                                             non_blocking=True)
-                    self._slice_evs[k].record(self._copy_stream)
+                    p.evs[k].record(p.copy_stream)
         # kernels per slice on the compute stream.  Streaming passes
         # (h2d=True) model fresh data and re-index newlines each pass;
         # device-resident re-scans reuse the staged line index.
-        for k, (s, e) in enumerate(self._slices):
+        for k, (s, e) in enumerate(p.slices):
             if h2d:
-                main.wait_event(self._slice_evs[k])
+                main.wait_event(p.evs[k])
                 self._submit(dev_data, s, e)
             else:
-                self._submit(dev_data, s, e, self._slice_pos[k])
+                self._submit(dev_data, s, e, p.pos[k])
         if h2d:
             ev_done.record(main)  # last reader of this pass's buffer
 
     # ---- wave-transposed staging (prototype; DRAGNET_XPOSE) ----
 
     def stage_xpose(self, buf=None):
-        """Wave-transposed staging for scan_kernel_x: records
-        length-sorted (aggregation is order-independent), 64
-        consecutive sorted records form a wave, each record's bytes
-        split into granules interleaved so granule g of lane l sits at
-        wave_base + g*64*gran + l*gran — a wave's window refills touch
-        64 CONSECUTIVE granules (coalesced) instead of 64 scattered
-        records.
+        """Wave-transposed staging for scan_kernel_x (engine/xpose.py).
 
-        Default: built ON DEVICE from the resident pool (torch sort +
-        cumsum + the xpose_build_kernel scatter) — no host staging
-        pass.  DRAGNET_XPOSE_HOST=1 selects the r1 numpy builder
-        (A/B + layout unit tests)."""
+        Default: built ON DEVICE from the resident pool — no host
+        staging pass.  DRAGNET_XPOSE_HOST=1 selects the r1 numpy
+        builder (A/B + layout unit tests)."""
         gran = _env_int("DRAGNET_XGRAN", 64)
         if gran not in (32, 64, 128):
             # the scan kernel is templated on the granule size; an
             # unsupported value would mismatch the staged layout
             raise ValueError("DRAGNET_XGRAN must be 32, 64 or 128")
         if os.environ.get("DRAGNET_XPOSE_HOST") == "1":
-            return self._stage_xpose_host(buf, gran)
-        torch = self.t
-        dev = self.eng.device
-        glog = gran.bit_length() - 1
-        if self._resident is None:
+            self._x = xpose.build_on_host(self.t, buf, gran,
+                                          self.eng.device)
+            return
+        if self._pool is None:
             if buf is None:
                 raise ValueError("no resident pool to transpose")
             self.stage_resident(buf)
-        n, _padded = self._resident
         # full-pool line index (the staged slice indexes cover slices)
-        pos, nlines = self._index(self._dev_data, 0, n)
-        nrec = int(nlines.item())  # one-time staging sync
-        if nrec == 0:
-            raise ValueError("no records")
-        pos = pos[:nrec].to(torch.int64)
-        starts = torch.empty_like(pos)
-        starts[0] = 0
-        starts[1:] = pos[:-1] + 1
-        lens_sorted, order = torch.sort(pos - starts)
-        starts_sorted = starts[order]
-        nslots = (nrec + 63) & ~63
-        nw = nslots // 64
-        slot_len = torch.full((nslots,), -1, dtype=torch.int32,
-                              device=dev)
-        slot_len[:nrec] = lens_sorted.to(torch.int32)
-        sstart = torch.zeros(nslots, dtype=torch.int32, device=dev)
-        sstart[:nrec] = starts_sorted.to(torch.int32)
-        # per-wave granule count from each wave's longest (last) lane
-        last = torch.clamp(
-            torch.arange(nw, device=dev, dtype=torch.int64) * 64 + 63,
-            max=nrec - 1)
-        gwl = torch.clamp((lens_sorted[last] + gran - 1) // gran, min=1)
-        stride = 64 * gran
-        wbase = torch.zeros(nw + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(gwl * stride, 0, out=wbase[1:])
-        total = int(wbase[-1].item()) + stride  # +slack
-        xb = torch.empty(total, dtype=torch.uint8, device=dev)
-        self.eng.ops.xpose_build(self._dev_data, sstart, slot_len,
-                                 wbase, nslots, glog, xb)
-        # the kernel reads wave_base[0, nw); the +1 entry is harmless
-        self._x = (xb, wbase, slot_len, nslots)
-
-    def _stage_xpose_host(self, buf, gran):
-        """r1 host-side numpy builder (kept for A/B and layout tests)."""
-        torch = self.t
-        dev = self.eng.device
-        xb, wave_base, slot_len, nslots, _n = _build_xpose_layout(
-            buf, gran)
-        self._x = (torch.from_numpy(xb).to(dev),
-                   torch.from_numpy(wave_base).to(dev),
-                   torch.from_numpy(slot_len.view(np.int32)).to(dev),
-                   nslots)
+        pos, nlines = self._index(self._dev_data, 0, self._pool.n)
+        self._x = xpose.build_on_device(self.t, self.eng.ops,
+                                        self._dev_data, pos, nlines, gran)
 
     def scan_xpose(self):
         """One scan pass over the wave-transposed staging."""
@@ -817,191 +707,46 @@ class _ScanContext(object):
         current stream before the reset's zeroing), which lets a caller
         software-pipeline host-side decode of step k with step k+1's
         copies/kernels (bench.py streaming mode)."""
-        r = self.state.extract_all()
-        h = {"cnt": r[0], "n_str": r[1], "n_num": r[2], "used": r[3],
-             "blob": r[4], "str_off": r[5], "str_len": r[6],
-             "numbers": r[7],
-             "aggs": [tuple(r[8 + 3 * m:11 + 3 * m])
-                      for m in range(len(queries))]}
-        torch = self.t
-        h["ev"] = torch.cuda.Event()
+        h = self.state.extract_all()
+        h["ev"] = self.t.cuda.Event()
         h["ev"].record()
         return h
 
     def decode_extracted(self, h, queries):
         """Host-side half of finalize(): wait for the extraction
         snapshot (ONLY — via its event, on a dedicated D2H stream, so
-        in-flight work from a subsequent step is not drained) and
-        decode into Aggregators."""
+        in-flight work from a subsequent step is not drained), copy it
+        to the host and decode into Aggregators (engine/decode.py)."""
         torch = self.t
         if self._fin_stream is None:
             self._fin_stream = torch.cuda.Stream(device=self.eng.device)
         with torch.cuda.stream(self._fin_stream):
             self._fin_stream.wait_event(h["ev"])
-            cnt = h["cnt"].cpu().numpy()
-            strings, numbers = self._decode_dicts(h)
-            hostk = []
-            for m, _q in enumerate(queries):
-                k_full, c_full, out_n = h["aggs"][m]
-                n_out = min(int(out_n.item()), self.agg_slots)
-                hostk.append((k_full[:n_out].cpu().numpy(),
-                              c_full[:n_out].cpu().numpy()))
-
-        aggs = []
-        for m, q in enumerate(queries):
-            k, c = hostk[m]
-            k = k.astype(np.uint32)
-            agg = Aggregator(q)
-            mc = cnt[C_GLOBAL_N + m * CM_N:
-                     C_GLOBAL_N + (m + 1) * CM_N]
-            agg.ninputs = int(mc[CM_AGG_IN])
-            agg.ndropped_nonnumeric = int(mc[CM_NONNUMERIC])
-            nk = len(q.breakdowns)
-            for i in range(k.shape[0]):
-                key = planmod.decode_key(k[i, :nk], q, strings, numbers)
-                v = c[i]
-                v = int(v) if float(v).is_integer() else float(v)
-                agg.table[key] = agg.table.get(key, 0) + v
-            aggs.append(agg)
-
-        stages = self._counter_stages(cnt, queries)
-        for name, c in stages:
-            if name == "Aggregator":
-                c["noutputs"] = aggs[0].noutputs()
-        return aggs, stages
+            host = {"cnt": h["cnt"].cpu().numpy()}
+            host.update(self._fetch_dicts(h))
+            host["aggs"] = []
+            for k_full, c_full, out_n in h["aggs"][:len(queries)]:
+                n_out = min(int(out_n.item()), k_full.shape[0])
+                host["aggs"].append((k_full[:n_out].cpu().numpy(),
+                                     c_full[:n_out].cpu().numpy()))
+        return decode.decode_snapshot(host, queries, self.cplan)
 
     @staticmethod
-    def _decode_dicts(h):
-        """The extraction's dictionaries in id order: (strings list,
-        numbers array).  The caller has waited for h["ev"]."""
+    def _fetch_dicts(h):
+        """Host copies of the extraction's dictionaries (decode.py's
+        `host` keys).  The caller has waited for h["ev"]."""
         n_str = int(h["n_str"].item())
         n_num = int(h["n_num"].item())
-        strings = []
+        host = {"n_str": n_str, "n_num": n_num}
         if n_str:
-            off = h["str_off"][:n_str].cpu().numpy().astype(np.uint32)
-            ln = h["str_len"][:n_str].cpu().numpy().astype(np.uint32)
+            host["str_off"] = h["str_off"][:n_str].cpu().numpy()
+            host["str_len"] = h["str_len"][:n_str].cpu().numpy()
             used = int(h["used"].item())
-            blob = h["blob"][:used].cpu().numpy().tobytes()
-            for i in range(n_str):
-                raw = blob[off[i]:off[i] + ln[i]]
-                strings.append(_decode_json_string(raw))
-        numbers = np.zeros(0)
+            host["blob"] = h["blob"][:used].cpu().numpy()
         if n_num:
-            numbers = h["numbers"][:n_num].cpu().numpy()
-        return strings, numbers
+            host["numbers"] = h["numbers"][:n_num].cpu().numpy()
+        return host
 
-    def _counter_stages(self, cnt, queries):
-        """Reconstruct the reference pipeline counter stages from the
-        device counters (mirrors scan_cpu.ScanPipeline.counter_stages)."""
-        cp = self.cplan
-        parsed = int(cnt[C_PARSED])
-        stages = [("json parser", {
-            "ninputs": int(cnt[C_LINES]), "noutputs": parsed,
-            "invalid json": int(cnt[C_INVALID_JSON])})]
-        if cp.data_format == "json":
-            stages.append(("SkinnerAdapterStream",
-                           {"ninputs": parsed, "noutputs": parsed}))
-        # program 0 is the ds filter; OP_TRUE means "no filter"
-        progs, bounds = cp.programs
-        if progs[bounds[0][0]][0] != planmod.OP_TRUE:
-            out, err = int(cnt[C_DS_FILTERED]), int(cnt[C_DS_FAILEDEVAL])
-            stages.append(("Datasource filter", {
-                "ninputs": parsed, "noutputs": parsed - out - err,
-                "nfilteredout": out, "nfailedeval": err}))
-        # metric 0's pipeline (what the CLI displays for scans)
-        q = queries[0]
-        mc = cnt[C_GLOBAL_N:C_GLOBAL_N + CM_N]
-        n = int(mc[CM_FILTER_IN])
-        if q.filter is not None:
-            out = n - int(mc[CM_FILTERED]) - int(mc[CM_FAILEDEVAL])
-            stages.append(("User filter", {
-                "ninputs": n, "noutputs": out,
-                "nfilteredout": int(mc[CM_FILTERED]),
-                "nfailedeval": int(mc[CM_FAILEDEVAL])}))
-            n = out
-        m0 = cp.metrics[0][0]
-        if m0[planmod.M_NSYNTH] > 0:  # has synthetic requirements
-            out = n - int(mc[CM_UNDEF]) - int(mc[CM_BADDATE])
-            stages.append(("Datetime parser", {
-                "ninputs": n, "noutputs": out,
-                "undef": int(mc[CM_UNDEF]),
-                "baddate": int(mc[CM_BADDATE])}))
-            n = out
-        if m0[planmod.M_HAS_TF]:  # time filter
-            stages.append(("Time filter", {
-                "ninputs": n, "noutputs": n - int(mc[CM_TIME_OUT]),
-                "nfilteredout": int(mc[CM_TIME_OUT]),
-                "nfailedeval": 0}))
-        stages.append(("Aggregator", {
-            "ninputs": int(mc[CM_AGG_IN]),
-            "noutputs": 0,  # patched by caller if needed
-            "nonnumeric": int(mc[CM_NONNUMERIC])}))
-        return stages
-
-
-def _build_xpose_layout(buf, gran=64):
-    """Numpy construction of the wave-transposed layout (see
-    _ScanContext.stage_xpose): returns (xbuf, wave_base, slot_len,
-    n_slots, n_records).  Byte p of slot r lives at
-    wave_base[r//64] + (p//gran)*(64*gran) + (r%64)*gran + p%gran."""
-    stride = 64 * gran
-    arr = np.frombuffer(buf, dtype=np.uint8)
-    nl = np.flatnonzero(arr == 10).astype(np.int64)
-    if nl.size == 0:
-        raise ValueError("no records")
-    starts = np.empty_like(nl)
-    starts[0] = 0
-    starts[1:] = nl[:-1] + 1
-    lens = (nl - starts).astype(np.int64)
-    n = int(lens.size)
-    order = np.argsort(lens, kind="stable")
-    nslots = (n + 63) & ~63
-    nw = nslots // 64
-    so = starts[order]
-    lo = lens[order]
-    # per-wave granule count: lengths are sorted, so a wave's max is
-    # its last real lane; the granule-row stride is a constant 4096
-    # (64 lanes x 64B), so variable wave sizes need no device change
-    last = np.minimum(np.arange(nw) * 64 + 63, n - 1)
-    gw = np.maximum(1, (lo[last] + gran - 1) // gran).astype(np.int64)
-    wave_base = np.zeros(nw, dtype=np.int64)
-    np.cumsum(gw[:-1] * stride, out=wave_base[1:])
-    total = int(wave_base[-1] + gw[-1] * stride) + stride  # +slack
-    xb = np.full(total, 10, dtype=np.uint8)
-    # build waves in batches of equal granule count (few distinct
-    # values after sorting) with one vectorized gather per batch
-    for g in np.unique(gw):
-        ws = np.flatnonzero(gw == g)
-        K = int(g) * gran
-        rsel = (ws[:, None] * 64 + np.arange(64)[None, :]).reshape(-1)
-        rl = np.where(rsel < n, lo[np.minimum(rsel, n - 1)], 0)
-        rs = np.where(rsel < n, so[np.minimum(rsel, n - 1)], 0)
-        idx = rs[:, None] + np.arange(K)[None, :]
-        np.minimum(idx, arr.size - 1, out=idx)
-        m = arr[idx]
-        m[np.arange(K)[None, :] >= rl[:, None]] = 10
-        # (wave, lane, granule, 64) -> (wave, granule, lane, 64)
-        blk = np.ascontiguousarray(
-            m.reshape(len(ws), 64, int(g), gran).transpose(0, 2, 1, 3)
-        ).reshape(len(ws), -1)
-        for i, w in enumerate(ws):
-            b = int(wave_base[w])
-            xb[b:b + K * 64] = blk[i]
-    slot_len = np.full(nslots, 0xFFFFFFFF, dtype=np.uint32)
-    slot_len[:n] = lo.astype(np.uint32)
-    return xb, wave_base, slot_len, nslots, n
-
-
-def _decode_json_string(raw):
-    """Decode raw in-record string bytes (may contain JSON escapes)
-    to the same Python string json.loads would produce."""
-    try:
-        s = raw.decode("utf-8")
-    except UnicodeDecodeError:
-        return raw.decode("utf-8", "replace")
-    if "\\" in s:
-        try:
-            return json.loads('"' + s + '"')
-        except ValueError:
-            return s
-    return s
+    @classmethod
+    def _decode_dicts(cls, h):
+        return decode.decode_dicts(cls._fetch_dicts(h))

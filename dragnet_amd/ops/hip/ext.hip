@@ -1,12 +1,12 @@
 // dragnet_amd MI355X scan engine — torch extension entry point.
 //
 // Single translation unit: includes the gfx950 kernels and exposes the
-// host launchers to Python.  All per-scan device state (plan buffers,
-// tables, dictionaries, counters) is bound ONCE into a ScanState, which
-// owns the tensors its descriptors point at; the per-launch methods
-// take only what changes from launch to launch.  The Python engine
-// (dragnet_amd/engine/gpu.py) allocates the tensors and keeps one
-// ScanState per scan context.
+// host launchers to Python.  All per-scan device state lives in a
+// ScanState: given the uploaded plan buffers and the table sizes it
+// allocates, owns and grows the tables, dictionaries and counters its
+// descriptors point at, so their layout is stated here alone; the
+// per-launch methods take only what changes from launch to launch.  The
+// Python engine (dragnet_amd/engine/gpu.py) keeps one per scan context.
 
 #include <torch/extension.h>
 #include <cstdlib>
@@ -39,17 +39,17 @@ void launch(const char* what, void (*kernel)(KArgs...), dim3 grid,
               hipGetErrorString(err));
 }
 
+// Largest grid of a scan launch; a dense table has one partial row per
+// workgroup, so this is its row count as well.
+constexpr uint32_t GRID_CAP = 2048;
+
 uint32_t grid_for(uint64_t n) {
-  return (uint32_t)std::min<uint64_t>((n + BLOCK - 1) / BLOCK, 2048);
+  return (uint32_t)std::min<uint64_t>((n + BLOCK - 1) / BLOCK, GRID_CAP);
 }
 
 int env_int(const char* name, int dflt) {
   const char* v = getenv(name);
   return v ? atoi(v) : dflt;
-}
-
-torch::Tensor tensor_at(const py::dict& d, const char* key) {
-  return py::cast<torch::Tensor>(d[key]);
 }
 
 // Dynamic LDS of one launch; the staging tile (if any) comes on top.
@@ -159,33 +159,26 @@ void xpose_build(torch::Tensor data, torch::Tensor sstart,
 }
 
 // The bound state of one scan context.  Built once from keyword
-// arguments; owns every tensor its PlanView / AggTable / StrDict /
-// NumDict descriptors point at, so their lifetime does not depend on
-// what Python happens to keep.  scan* and reset do no allocation, host
-// sync or environment read — they are safe inside a graph capture.
+// arguments; allocates and owns every tensor its PlanView / AggTable /
+// StrDict / NumDict descriptors point at, so their lifetime does not
+// depend on what Python happens to keep.  scan* and reset do no
+// allocation, host sync or environment read — they are safe inside a
+// graph capture.
 class ScanState {
  public:
-  // plan:  the compiled plan's device buffers and scalars by name
-  // states/keys/counts: per-metric aggregation tables
-  // partials (empty, or one per metric): [prows, nslots] f64 dense
-  //   partial matrices — enables dense accumulation + the MFMA reduce
-  // sdict/ndict: the string / number dictionaries' tensors by name
-  ScanState(py::dict plan, std::vector<torch::Tensor> states,
-            std::vector<torch::Tensor> keys,
-            std::vector<torch::Tensor> counts,
-            std::vector<torch::Tensor> partials, py::dict sdict,
-            py::dict ndict, torch::Tensor counters)
-      : states_(std::move(states)), keys_(std::move(keys)),
-        counts_(std::move(counts)), partials_(std::move(partials)),
-        counters_(std::move(counters)) {
-    CHECK_GPU(counters_);
+  // plan:  the compiled plan's device buffers and scalars by name; the
+  //        state lives on their device
+  // agg_slots: of each metric's table; dict_slots: of either dictionary
+  // dense: also a [GRID_CAP, agg_slots] f64 partial matrix per metric —
+  //        enables dense accumulation + the MFMA reduce
+  ScanState(py::dict plan, int64_t agg_slots, int64_t dict_slots,
+            int64_t dict_data_bytes, bool dense)
+      : dense_(dense) {
     auto ptr = [&](py::dict& d, const char* key) {
-      owned_.push_back(tensor_at(d, key));
+      owned_.push_back(py::cast<torch::Tensor>(d[key]));
       return owned_.back().data_ptr();
     };
     PlanView& P = args_.P;
-    StrDict& sd = args_.sdict;
-    NumDict& nd = args_.ndict;
     // the ONE place a PlanView is filled (columnar_query adjusts a copy)
     P.field_sigs = (const uint64_t*)ptr(plan, "field_sigs");
     P.nf = (int)owned_.back().numel();
@@ -210,35 +203,29 @@ class ScanState {
         (uint64_t)py::cast<int64_t>(plan["fields_parent_sig"]);
     args_.data_format_skinner = py::cast<bool>(plan["skinner"]) ? 1 : 0;
 
-    // dictionaries: every tensor is a named member (reset, extract_all
-    // and grow_* use the tensors themselves)
-    sd_used_ = tensor_at(sdict, "used");
-    sd_next_ = tensor_at(sdict, "next");
-    CHECK_GPU(sd_used_);
-    CHECK_GPU(sd_next_);
-    sd.data_used = (uint32_t*)sd_used_.data_ptr();
-    sd.next_id = (uint32_t*)sd_next_.data_ptr();
-    bind_sdict_slots(tensor_at(sdict, "state"), tensor_at(sdict, "hash"),
-                     tensor_at(sdict, "id"), tensor_at(sdict, "off"),
-                     tensor_at(sdict, "len"));
-    bind_sdict_data(tensor_at(sdict, "data"));
-
-    nd_next_ = tensor_at(ndict, "next");
-    CHECK_GPU(nd_next_);
-    nd.next_id = (uint32_t*)nd_next_.data_ptr();
-    bind_ndict_slots(tensor_at(ndict, "state"), tensor_at(ndict, "bits"),
-                     tensor_at(ndict, "id"));
-
-    // per-metric table descriptors
-    size_t nm = states_.size();
-    TORCH_CHECK((int)nm == P.nm && keys_.size() == nm &&
-                    counts_.size() == nm &&
-                    (partials_.empty() || partials_.size() == nm),
-                "one table (and partial) per metric");
     // every plan descriptor holds a raw device pointer
-    for (auto* group : {&partials_, &owned_})
-      for (auto& t : *group) CHECK_GPU(t);
+    for (auto& t : owned_) CHECK_GPU(t);
+    device_ = owned_.front().device();
+
+    // tables, dictionaries and counters: every tensor is a member
+    // (reset, extract_all and grow_* use the tensors themselves)
+    check_slots(agg_slots, "agg table", AGG_LOG2);
+    check_slots(dict_slots, "sdict", DICT_LOG2);
+    check_bytes(dict_data_bytes);
+    states_.resize(P.nm);
+    keys_.resize(P.nm);
+    counts_.resize(P.nm);
+    if (dense_) partials_.resize(P.nm);
+    for (int m = 0; m < P.nm; m++) alloc_agg(m, agg_slots);
+    alloc_sdict(dict_slots);
+    alloc_ndict(dict_slots);
+    sd_data_ = zeros({dict_data_bytes}, U8);
+    sd_used_ = zeros({1}, I32);
+    sd_next_ = zeros({1}, I32);
+    nd_next_ = zeros({1}, I32);
+    counters_ = zeros({C_GLOBAL_N + P.nm * CM_N}, I64);
     bind_tables();
+    bind_dicts();
     args_.counters = (unsigned long long*)counters_.data_ptr();
 
     // experiment knobs: read once, here — never per launch.  Default 4
@@ -355,63 +342,76 @@ class ScanState {
   // dictionary cursors/blob, the dictionary extractions, and the
   // no-sync per-metric aggregate extraction, enqueued on the current
   // stream in one binding call instead of ~10 python dispatches.
-  // Returns [cnt, n_str, n_num, used, blob, str_off, str_len, numbers,
-  // then (keys, counts, n) per metric]; the per-metric buffers are
+  // aggs is a list of (keys, counts, n) per metric; its buffers are
   // full-capacity and the caller slices by n after its own sync.
-  std::vector<torch::Tensor> extract_all() {
+  py::dict extract_all() {
     // dense mode: fold the per-workgroup partial matrices into count[]
     // (MFMA column-sum) before the table extraction below reads them
     for (const AggTable& T : tables_) dense_reduce(T);
     const StrDict& sd = args_.sdict;
     const NumDict& nd = args_.ndict;
-    auto i32 = torch::dtype(torch::kInt32).device(counters_.device());
-    auto f64 = torch::dtype(torch::kFloat64).device(counters_.device());
-    std::vector<torch::Tensor> out;
-    out.push_back(counters_.clone());
-    out.push_back(sd_next_.clone());
-    out.push_back(nd_next_.clone());
-    out.push_back(sd_used_.clone());
+    py::dict out;
+    out["cnt"] = counters_.clone();
+    out["n_str"] = sd_next_.clone();
+    out["n_num"] = nd_next_.clone();
+    out["used"] = sd_used_.clone();
     // the dictionary byte blob is bump-allocated from 0 each scan, so
     // the NEXT step overwrites it — snapshot now
-    out.push_back(sd_data_.clone());
+    out["blob"] = sd_data_.clone();
 
     long n_sids = std::max<long>(sd.nslots, 1);
-    auto str_off = torch::zeros({n_sids}, i32);
-    auto str_len = torch::zeros({n_sids}, i32);
+    auto str_off = zeros({n_sids}, I32);
+    auto str_len = zeros({n_sids}, I32);
     if (sd.nslots > 0)
       launch("extract_strdict", extract_strdict_kernel,
              dim3((sd.nslots + 255) / 256), dim3(256), 0, sd,
              (uint32_t*)str_off.data_ptr(), (uint32_t*)str_len.data_ptr(),
              sd.nslots);
-    out.push_back(str_off);
-    out.push_back(str_len);
+    out["str_off"] = str_off;
+    out["str_len"] = str_len;
 
-    auto numbers = torch::zeros({std::max<long>(nd.nslots, 1)}, f64);
+    auto numbers = zeros({std::max<long>(nd.nslots, 1)}, F64);
     if (nd.nslots > 0)
       launch("extract_numdict", extract_numdict_kernel,
              dim3((nd.nslots + 255) / 256), dim3(256), 0, nd,
              (double*)numbers.data_ptr(), nd.nslots);
-    out.push_back(numbers);
+    out["numbers"] = numbers;
 
+    py::list aggs;
     for (const AggTable& T : tables_) {
       long max_out = T.nslots;
-      auto out_keys = torch::zeros({max_out, (long)MAX_KEY}, i32);
-      auto out_counts = torch::zeros({max_out}, f64);
-      auto out_n = torch::zeros({1}, i32);
+      auto out_keys = zeros({max_out, (long)MAX_KEY}, I32);
+      auto out_counts = zeros({max_out}, F64);
+      auto out_n = zeros({1}, I32);
       launch("extract_agg", extract_agg_kernel,
              dim3((T.nslots + 255) / 256), dim3(256), 0, T,
              (uint32_t*)out_keys.data_ptr(),
              (double*)out_counts.data_ptr(), (uint32_t*)out_n.data_ptr(),
              (uint32_t)max_out);
-      out.insert(out.end(), {out_keys, out_counts, out_n});
+      aggs.append(py::make_tuple(out_keys, out_counts, out_n));
     }
+    out["aggs"] = aggs;
     return out;
   }
 
+  // Slots / bytes by name, as capacity.CapacityPlanner.names has them.
+  py::dict sizes() const {
+    py::dict out;
+    for (size_t m = 0; m < tables_.size(); m++)
+      out[py::str("agg" + std::to_string(m))] = tables_[m].nslots;
+    out["sdict"] = args_.sdict.nslots;
+    out["sdata"] = args_.sdict.data_cap;
+    out["ndict"] = args_.ndict.nslots;
+    return out;
+  }
+
+  torch::Tensor counters() const { return counters_; }
+
   // ---- in-place growth (hash path only; engine/capacity.py plans it) ----
-  // Each grow_* takes freshly ZEROED tensors of the new size, enqueues
-  // the rehash (scan_rehash.h) on the current stream and rebinds the
-  // descriptors; the old tensors stay referenced until that launch is
+  // Each grow_* validates the new size (a rejected call changes
+  // nothing), allocates zeroed tensors of that size, rebinds the
+  // descriptors and enqueues the rehash (scan_rehash.h) on the current
+  // stream; the old tensors stay referenced until that launch is
   // enqueued and are then dropped (the allocator reuses them in stream
   // order).  lds_, the launch knobs and the counters are unaffected: a
   // placement that cannot be made bumps C_OVERFLOW, nothing else does.
@@ -428,161 +428,161 @@ class ScanState {
     return torch::cat(parts);
   }
 
-  void grow_agg(int64_t m, torch::Tensor state, torch::Tensor keys,
-                torch::Tensor count) {
-    TORCH_CHECK(partials_.empty(), "dense tables do not grow");
+  void grow_agg(int64_t m, int64_t new_slots) {
+    TORCH_CHECK(!dense_, "dense tables do not grow");
     TORCH_CHECK(m >= 0 && (size_t)m < tables_.size(), "no such metric");
     AggTable old = tables_[m];
-    check_growth(old.nslots, checked_slots(state, "agg table"));
+    check_slots(new_slots, "agg table", AGG_LOG2, old.nslots);
     std::vector<torch::Tensor> keep = {states_[m], keys_[m], counts_[m]};
-    states_[m] = std::move(state);
-    keys_[m] = std::move(keys);
-    counts_[m] = std::move(count);
+    growing("agg" + std::to_string(m), old.nslots, new_slots,
+            [&] { alloc_agg(m, new_slots); });
     bind_tables();
     launch("rehash_agg", rehash_agg_kernel, dim3((old.nslots + 255) / 256),
            dim3(256), 0, old, tables_[m], overflow_ptr());
   }
 
-  void grow_sdict(torch::Tensor state, torch::Tensor hash,
-                  torch::Tensor id, torch::Tensor off, torch::Tensor len) {
+  void grow_sdict(int64_t new_slots) {
     StrDict old = args_.sdict;
-    check_growth(old.nslots, checked_slots(state, "sdict"));
+    check_slots(new_slots, "sdict", DICT_LOG2, old.nslots);
     std::vector<torch::Tensor> keep = {sd_state_, sd_hash_, sd_id_,
                                        sd_off_, sd_len_};
-    bind_sdict_slots(std::move(state), std::move(hash), std::move(id),
-                     std::move(off), std::move(len));
+    growing("sdict", old.nslots, new_slots, [&] { alloc_sdict(new_slots); });
+    bind_dicts();
     launch("rehash_strdict", rehash_strdict_kernel,
            dim3((old.nslots + 255) / 256), dim3(256), 0, old, args_.sdict,
            overflow_ptr());
   }
 
   // The payload blob moves to the same offsets: a plain device copy.
-  void grow_sdata(torch::Tensor data) {
+  void grow_sdata(int64_t new_bytes) {
     torch::Tensor old = sd_data_;
-    TORCH_CHECK(data.numel() > old.numel(),
-                "string payload buffer may only grow");
-    bind_sdict_data(std::move(data));
-    hipError_t e = hipMemcpyAsync(sd_data_.data_ptr(), old.data_ptr(),
-                                  (size_t)old.numel(),
-                                  hipMemcpyDeviceToDevice,
-                                  current_stream());
+    check_bytes(new_bytes, old.numel());
+    growing("sdata", old.numel(), new_bytes,
+            [&] { sd_data_ = zeros({new_bytes}, U8); });
+    bind_dicts();
+    hipError_t e = hipMemcpyAsync(
+        sd_data_.data_ptr(), old.data_ptr(), (size_t)old.numel(),
+        hipMemcpyDeviceToDevice, current_stream());
     TORCH_CHECK(e == hipSuccess, "payload copy failed: ",
                 hipGetErrorString(e));
   }
 
-  void grow_ndict(torch::Tensor state, torch::Tensor bits,
-                  torch::Tensor id) {
+  void grow_ndict(int64_t new_slots) {
     NumDict old = args_.ndict;
-    check_growth(old.nslots, checked_slots(state, "ndict"));
+    check_slots(new_slots, "ndict", DICT_LOG2, old.nslots);
     std::vector<torch::Tensor> keep = {nd_state_, nd_bits_, nd_id_};
-    bind_ndict_slots(std::move(state), std::move(bits), std::move(id));
+    growing("ndict", old.nslots, new_slots, [&] { alloc_ndict(new_slots); });
+    bind_dicts();
     launch("rehash_numdict", rehash_numdict_kernel,
            dim3((old.nslots + 255) / 256), dim3(256), 0, old, args_.ndict,
            overflow_ptr());
   }
 
  private:
-  // A descriptor array over `n` elements of `dtype` on the GPU.
-  static void* checked_ptr(const torch::Tensor& t, int64_t n,
-                           torch::ScalarType dtype, const char* what) {
-    TORCH_CHECK(t.is_cuda() && t.is_contiguous() &&
-                    t.scalar_type() == dtype && t.numel() == n,
-                what, ": need a contiguous GPU tensor of ", n,
-                " elements");
-    return t.data_ptr();
+  static constexpr auto I32 = torch::kInt32, I64 = torch::kInt64,
+                        F64 = torch::kFloat64, U8 = torch::kUInt8;
+
+  torch::Tensor zeros(at::IntArrayRef shape, torch::ScalarType dtype) const {
+    return torch::zeros(shape, torch::dtype(dtype).device(device_));
   }
 
-  // slot counts are masks (power of two) and uint32 on the device
-  static uint32_t checked_slots(const torch::Tensor& state,
-                                const char* what) {
-    int64_t n = state.numel();
-    TORCH_CHECK(n > 0 && (n & (n - 1)) == 0 && n <= ((int64_t)1 << 31),
-                what, ": slot count must be a power of two <= 2^31");
-    return (uint32_t)n;
+  // A requested slot count: a mask (power of two), uint32 on the device
+  // (AGG_LOG2: an aggregation table's keys are indexed slot * MAX_KEY in
+  // uint32), and more than the present count where a table grows.
+  static constexpr int DICT_LOG2 = 31, AGG_LOG2 = 29;
+  static void check_slots(int64_t n, const char* what, int max_log2,
+                          int64_t old = 0) {
+    TORCH_CHECK(n > 0 && (n & (n - 1)) == 0 && (n >> max_log2) <= 1, what,
+                ": slot count must be a power of two <= 2^", max_log2);
+    TORCH_CHECK(n > old, "a table may only grow (", old, " -> ", n,
+                " slots)");
   }
 
-  static void check_growth(uint32_t old_slots, uint32_t new_slots) {
-    TORCH_CHECK(new_slots > old_slots, "a table may only grow (", old_slots,
-                " -> ", new_slots, " slots)");
+  // offsets into the payload are uint32
+  static void check_bytes(int64_t n, int64_t old = -1) {
+    TORCH_CHECK(n <= (int64_t)0xFFFFFFFFll,
+                "string payload buffer exceeds 32-bit offsets");
+    TORCH_CHECK(n > old, "string payload buffer may only grow");
+  }
+
+  // Run one structure's allocation for a growth; a failed device
+  // allocation has changed no member and is reported as a RuntimeError.
+  template <class Alloc>
+  static void growing(const std::string& name, int64_t old_size,
+                      int64_t new_size, Alloc&& alloc) {
+    try {
+      alloc();
+    } catch (const c10::OutOfMemoryError& e) {
+      std::string why = e.what_without_backtrace();
+      TORCH_CHECK(false, "cannot grow ", name, " from ", old_size, " to ",
+                  new_size, ": device allocation failed (",
+                  why.substr(0, why.find('\n')), ")");
+    }
   }
 
   unsigned long long* overflow_ptr() {
     return (unsigned long long*)counters_.data_ptr() + C_OVERFLOW;
   }
 
-  void bind_sdict_slots(torch::Tensor state, torch::Tensor hash,
-                        torch::Tensor id, torch::Tensor off,
-                        torch::Tensor len) {
+  // alloc_*: one structure's zeroed tensors at a checked size.  The
+  // right-hand side allocates them all before the first member changes.
+  void alloc_agg(size_t m, int64_t n) {
+    std::tie(states_[m], keys_[m], counts_[m]) = std::make_tuple(
+        zeros({n}, I32), zeros({n * MAX_KEY}, I32), zeros({n}, F64));
+    if (dense_) partials_[m] = zeros({GRID_CAP, n}, F64);
+  }
+
+  void alloc_sdict(int64_t n) {
+    std::tie(sd_state_, sd_hash_, sd_id_, sd_off_, sd_len_) =
+        std::make_tuple(zeros({n}, I32), zeros({n}, I64), zeros({n}, I32),
+                        zeros({n}, I32), zeros({n}, I32));
+  }
+
+  void alloc_ndict(int64_t n) {
+    std::tie(nd_state_, nd_bits_, nd_id_) =
+        std::make_tuple(zeros({n}, I32), zeros({n}, I64), zeros({n}, I32));
+  }
+
+  // (Re)build the dictionary descriptors from their tensors.
+  void bind_dicts() {
     StrDict& sd = args_.sdict;
-    int64_t n = checked_slots(state, "sdict");
-    sd.state = (uint32_t*)checked_ptr(state, n, torch::kInt32, "sdict.state");
-    sd.hash = (uint64_t*)checked_ptr(hash, n, torch::kInt64, "sdict.hash");
-    sd.id = (uint32_t*)checked_ptr(id, n, torch::kInt32, "sdict.id");
-    sd.off = (uint32_t*)checked_ptr(off, n, torch::kInt32, "sdict.off");
-    sd.len = (uint32_t*)checked_ptr(len, n, torch::kInt32, "sdict.len");
-    sd.nslots = (uint32_t)n;
-    sd_state_ = std::move(state);
-    sd_hash_ = std::move(hash);
-    sd_id_ = std::move(id);
-    sd_off_ = std::move(off);
-    sd_len_ = std::move(len);
-  }
-
-  void bind_sdict_data(torch::Tensor data) {
-    // offsets into the payload are uint32
-    TORCH_CHECK(data.numel() <= (int64_t)0xFFFFFFFFll,
-                "string payload buffer exceeds 32-bit offsets");
-    args_.sdict.data = (uint8_t*)checked_ptr(data, data.numel(),
-                                             torch::kUInt8, "sdict.data");
-    args_.sdict.data_cap = (uint32_t)data.numel();
-    sd_data_ = std::move(data);
-  }
-
-  void bind_ndict_slots(torch::Tensor state, torch::Tensor bits,
-                        torch::Tensor id) {
+    sd.state = (uint32_t*)sd_state_.data_ptr();
+    sd.hash = (uint64_t*)sd_hash_.data_ptr();
+    sd.id = (uint32_t*)sd_id_.data_ptr();
+    sd.off = (uint32_t*)sd_off_.data_ptr();
+    sd.len = (uint32_t*)sd_len_.data_ptr();
+    sd.nslots = (uint32_t)sd_state_.numel();
+    sd.data = (uint8_t*)sd_data_.data_ptr();
+    sd.data_cap = (uint32_t)sd_data_.numel();
+    sd.data_used = (uint32_t*)sd_used_.data_ptr();
+    sd.next_id = (uint32_t*)sd_next_.data_ptr();
     NumDict& nd = args_.ndict;
-    int64_t n = checked_slots(state, "ndict");
-    nd.state = (uint32_t*)checked_ptr(state, n, torch::kInt32, "ndict.state");
-    nd.bits = (uint64_t*)checked_ptr(bits, n, torch::kInt64, "ndict.bits");
-    nd.id = (uint32_t*)checked_ptr(id, n, torch::kInt32, "ndict.id");
-    nd.nslots = (uint32_t)n;
-    nd_state_ = std::move(state);
-    nd_bits_ = std::move(bits);
-    nd_id_ = std::move(id);
+    nd.state = (uint32_t*)nd_state_.data_ptr();
+    nd.bits = (uint64_t*)nd_bits_.data_ptr();
+    nd.id = (uint32_t*)nd_id_.data_ptr();
+    nd.nslots = (uint32_t)nd_state_.numel();
+    nd.next_id = (uint32_t*)nd_next_.data_ptr();
   }
 
   // (Re)build the per-metric table descriptors from states_/keys_/
-  // counts_/partials_ and upload them.  keys are indexed slot * MAX_KEY
-  // in uint32 on the device.
+  // counts_/partials_ and upload them.
   void bind_tables() {
     size_t nm = states_.size();
     tables_.resize(nm);
     for (size_t m = 0; m < nm; m++) {
       AggTable& t = tables_[m];
-      int64_t n = checked_slots(states_[m], "agg table");
-      TORCH_CHECK(n <= ((int64_t)1 << 29),
-                  "agg table: slot * MAX_KEY must fit uint32");
-      t.state = (uint32_t*)checked_ptr(states_[m], n, torch::kInt32,
-                                       "agg state");
-      t.keys = (uint32_t*)checked_ptr(keys_[m], n * MAX_KEY, torch::kInt32,
-                                      "agg keys");
-      t.count = (double*)checked_ptr(counts_[m], n, torch::kFloat64,
-                                     "agg count");
-      t.nslots = (uint32_t)n;
-      t.partial = nullptr;
-      t.prows = 0;
+      t.state = (uint32_t*)states_[m].data_ptr();
+      t.keys = (uint32_t*)keys_[m].data_ptr();
+      t.count = (double*)counts_[m].data_ptr();
+      t.nslots = (uint32_t)states_[m].numel();
+      t.partial = dense_ ? (double*)partials_[m].data_ptr() : nullptr;
+      t.prows = dense_ ? GRID_CAP : 0;
       t.pad_ = 0;
-      if (!partials_.empty()) {
-        TORCH_CHECK(partials_[m].size(1) == (long)t.nslots,
-                    "partial width != nslots");
-        t.partial = (double*)partials_[m].data_ptr();
-        t.prows = (uint32_t)partials_[m].size(0);
-      }
     }
     auto host = torch::empty({(long)(nm * sizeof(AggTable))},
                              torch::dtype(torch::kUInt8));
     memcpy(host.data_ptr(), tables_.data(), nm * sizeof(AggTable));
-    table_descs_ = host.to(counters_.device());
+    table_descs_ = host.to(device_);
     args_.tables = (AggTable*)table_descs_.data_ptr();
   }
 
@@ -608,6 +608,8 @@ class ScanState {
   torch::Tensor sd_data_, sd_used_, sd_next_;
   torch::Tensor nd_state_, nd_bits_, nd_id_, nd_next_;
   torch::Tensor counters_, table_descs_;
+  c10::Device device_ = c10::kCPU;  // of the plan tensors
+  const bool dense_;
   // prebuilt launch arguments: the PlanView, StrDict and NumDict, the
   // table/counter pointers and the tile size; a launch copies them and
   // sets only its own input fields
@@ -629,13 +631,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("ns") = 0, py::arg("columnar") = false,
         "dynamic LDS bytes of a scan / columnar launch (host only)");
   py::class_<dn::ScanState>(m, "ScanState")
-      .def(py::init<py::dict, std::vector<torch::Tensor>,
-                    std::vector<torch::Tensor>, std::vector<torch::Tensor>,
-                    std::vector<torch::Tensor>, py::dict, py::dict,
-                    torch::Tensor>(),
-           py::kw_only(), py::arg("plan"), py::arg("states"),
-           py::arg("keys"), py::arg("counts"), py::arg("partials"),
-           py::arg("sdict"), py::arg("ndict"), py::arg("counters"))
+      .def(py::init<py::dict, int64_t, int64_t, int64_t, bool>(),
+           py::kw_only(), py::arg("plan"), py::arg("agg_slots"),
+           py::arg("dict_slots"), py::arg("dict_data_bytes"),
+           py::arg("dense"))
       .def("scan", &dn::ScanState::scan, py::arg("data"),
            py::arg("nl_pos"), py::arg("nlines"), py::arg("first_start"),
            "fused NDJSON scan over one chunk")
@@ -650,14 +649,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("occupancy", &dn::ScanState::occupancy,
            "device int64 [ready slots per metric..., string ids, "
            "payload bytes, number ids]")
+      .def("sizes", &dn::ScanState::sizes)
+      .def_property_readonly("counters", &dn::ScanState::counters)
       .def("grow_agg", &dn::ScanState::grow_agg, py::arg("metric"),
-           py::arg("state"), py::arg("keys"), py::arg("count"),
-           "rehash one metric's table into larger zeroed tensors")
-      .def("grow_sdict", &dn::ScanState::grow_sdict, py::arg("state"),
-           py::arg("hash"), py::arg("id"), py::arg("off"), py::arg("len"))
-      .def("grow_sdata", &dn::ScanState::grow_sdata, py::arg("data"))
-      .def("grow_ndict", &dn::ScanState::grow_ndict, py::arg("state"),
-           py::arg("bits"), py::arg("id"));
+           py::arg("new_slots"),
+           "rehash one metric's table into a larger zeroed one")
+      .def("grow_sdict", &dn::ScanState::grow_sdict, py::arg("new_slots"))
+      .def("grow_sdata", &dn::ScanState::grow_sdata, py::arg("new_bytes"))
+      .def("grow_ndict", &dn::ScanState::grow_ndict, py::arg("new_slots"));
   m.attr("MAX_KEY") = (int)dn::MAX_KEY;
   m.attr("MAX_FIELDS") = (int)dn::MAX_FIELDS;
 }

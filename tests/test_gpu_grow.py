@@ -343,3 +343,78 @@ def test_low_cardinality_plans_no_growth(engines, lines50k, monkeypatch):
     assert_same(c, g)
     assert g.gpu_stats == {"restarts": 0, "agg": [0], "sdict": 0,
                            "sdata": 0, "ndict": 0}
+
+
+def _small_context(gpu, qs, **kw):
+    from dragnet_amd.engine import plan as planmod
+    from dragnet_amd.engine.gpu import _ScanContext
+    return _ScanContext(gpu, planmod.compile_plan(qs), agg_slots=128,
+                        dict_slots=128, dict_data_cap=4096, **kw)
+
+
+def _values(aggs):
+    return [{tuple(sorted(p["fields"].items())): p["value"]
+             for p in a.points()} for a in aggs]
+
+
+# 11
+def test_state_sizes_and_rejected_growth(engines, monkeypatch):
+    """The state reports its sizes under the planner's names; a growth
+    it rejects (a host-side argument check) changes nothing, and the
+    context scans and grows as if it had not been asked."""
+    from dragnet_amd.tools.mktestdata import generate_lines
+    cpu, gpu = engines
+    monkeypatch.setenv("DRAGNET_GROW_MIN_RECORDS", "64")
+    qs = [q("req.method,res.statusCode"), q("host")]
+    ctx = _small_context(gpu, qs, growable=True)
+    st = ctx.state
+    sizes0 = {"agg0": 128, "agg1": 128, "sdict": 128, "sdata": 4096,
+              "ndict": 128}
+    assert st.sizes() == sizes0
+    assert list(st.sizes()) == ctx.planner.names
+    assert st.sizes() == ctx.planner.size
+
+    for call, text in (
+            (lambda: st.grow_agg(0, 128), "a table may only grow"),
+            (lambda: st.grow_agg(0, 64), "a table may only grow"),
+            (lambda: st.grow_sdict(192), "must be a power of two"),
+            (lambda: st.grow_sdata(4096), "buffer may only grow"),
+            (lambda: st.grow_agg(2, 256), "no such metric")):
+        with pytest.raises(RuntimeError, match=text):
+            call()
+    assert st.sizes() == sizes0
+
+    blob = b"".join(generate_lines(200, seed=11))
+    want = cpu.scan([], qs, byte_source=[blob])
+    ctx.feed(blob)
+    aggs, _stages = ctx.finalize(qs)
+    assert not ctx.overflowed()
+    assert [a.points() for a in aggs] == \
+        [a.points() for a in want.aggregators]
+    once = _values(aggs)
+    sizes1 = st.sizes()
+
+    ctx.grow("agg1", 512)
+    assert st.sizes() == dict(sizes1, agg1=512) == ctx.planner.size
+    ctx.feed(blob)
+    aggs, _stages = ctx.finalize(qs)
+    assert not ctx.overflowed()
+    assert _values(aggs) == [{k: 2 * v for k, v in m.items()}
+                             for m in once]
+
+
+# 12
+def test_dense_state_does_not_grow(engines):
+    from dragnet_amd.tools.mktestdata import generate_lines
+    cpu, gpu = engines
+    qs = [q("req.method,res.statusCode")]
+    ctx = _small_context(gpu, qs, dense=True)
+    assert ctx.dense
+    with pytest.raises(RuntimeError, match="dense tables do not grow"):
+        ctx.state.grow_agg(0, 256)
+    blob = b"".join(generate_lines(200, seed=11))
+    ctx.feed(blob)
+    aggs, _stages = ctx.finalize(qs)
+    assert not ctx.overflowed()
+    assert aggs[0].points() == \
+        cpu.scan([], qs, byte_source=[blob]).aggregators[0].points()

@@ -5,7 +5,7 @@ cursor may peek past a record's end)."""
 
 import numpy as np
 
-from dragnet_amd.engine.gpu import _build_xpose_layout
+from dragnet_amd.engine.xpose import _build_xpose_layout
 
 
 def detranspose(xb, wave_base, slot_len, r, gran=64):
