@@ -33,9 +33,10 @@ def scan(dsname, filter=None, breakdowns=None, time_after=None,
 
 
 def build(dsname, interval="day", time_after=None, time_before=None,
-          cfg=None, engine=None):
+          cfg=None, engine=None, columnar=None):
     """Materialize indexes for the datasource's configured metrics;
-    returns the index files written."""
+    returns the index files written.  columnar=True also writes a
+    columnar sidecar beside each (None: DRAGNET_INDEX_COLUMNAR)."""
     cfg = cfg or mod_config.load_config()
     backend = datasource_for_name(dsname, cfg=cfg, engine=engine)
     metrics = [m.serialize(skip_datasource=True)
@@ -44,8 +45,9 @@ def build(dsname, interval="day", time_after=None, time_before=None,
     for m in metrics:
         m["breakdowns"] = parse_fields(m.get("breakdowns", []))
     after_ms, before_ms = parse_time_bounds(time_after, time_before)
+    kw = {} if columnar is None else {"columnar": columnar}
     return backend.build(metrics, interval=interval,
-                         after_ms=after_ms, before_ms=before_ms)
+                         after_ms=after_ms, before_ms=before_ms, **kw)
 
 
 def query(dsname, filter=None, breakdowns=None, interval="day",

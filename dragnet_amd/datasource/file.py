@@ -200,9 +200,10 @@ class FileDatasource(object):
         return points, result.stages
 
     def build(self, metrics, interval="day", after_ms=None,
-              before_ms=None, dry_run=False):
+              before_ms=None, dry_run=False, columnar=None):
         """Materialize indexes (reference lib/datasource-file.js:307-432).
-        Returns the list of index files written."""
+        Returns the list of index files written.  columnar: also write
+        a columnar sidecar beside each (None: DRAGNET_INDEX_COLUMNAR)."""
         if not self.ds.index_path:
             raise ValueError(
                 'datasource is missing "indexPath" for index operations')
@@ -211,18 +212,23 @@ class FileDatasource(object):
         if rv is None:
             return None
         points, _stages = rv
-        return write_index(self.ds.index_path, metrics, interval, points)
+        return write_index(self.ds.index_path, metrics, interval, points,
+                           columnar=columnar)
 
     # ---- index querying ----
 
     def _find_index_files(self, query, interval, counters=None):
+        """The index files of the tree; the columnar sidecars beside
+        them are no index files and are not seen."""
+        from ..index.columnar import is_sidecar_name
         if interval == "all":
             root = os.path.join(self.ds.index_path, "all")
             return find_files([root], counters=counters)
         _, _, subdir, pattern, _ = INTERVALS[interval]
         root = os.path.join(self.ds.index_path, subdir)
         return find_data_files(root, pattern, query.after_ms,
-                               query.before_ms, counters=counters)
+                               query.before_ms, counters=counters,
+                               ignore=is_sidecar_name)
 
     def query(self, query, interval="day", dry_run=False, out=None):
         """Answer a query from the index tree: per-file partials merged
@@ -259,7 +265,16 @@ class FileDatasource(object):
         # only above a measured row-count threshold (small tables are
         # dominated by per-file setup; see profiles/r02_k7.md)
         mode = os.environ.get("DRAGNET_INDEX_GPU", "auto")
+        # files with a usable columnar sidecar are answered together,
+        # one launch per group; the rest one by one, as ever
+        served = self._query_sidecars([p for p, _ in files], eff, mode)
+        from ..index.columnar import STATS
+        STATS["other_files"] += len(files) - len(served)
         for path, _st in files:
+            if path in served:
+                for p in served[path].points():
+                    final.write(p)
+                continue
             try:
                 iq = IndexQuerier(path)
             except IndexError_ as e:
@@ -289,7 +304,65 @@ class FileDatasource(object):
         ]
         result = ScanResult([final], stages, [p for p, _ in files])
         result.errors = nerrors
+        result.sidecar_files = sorted(served)
         return result
+
+    def _query_sidecars(self, paths, query, mode):
+        """Answer the query for every index file that has a usable
+        columnar sidecar (index/columnar.py): the sidecars are merged
+        per metric group and each group is one GpuEngine.coded_query
+        launch.  Returns {path: that file's partial Aggregator}; a file
+        not in it is served by the per-file loop.
+
+        Only a GPU engine reads sidecars.  "1" takes this path wherever
+        sidecars are usable; "auto" only from
+        DRAGNET_INDEX_COLUMNAR_ROWS sidecar rows up (counted from the
+        headers).  A group with a backslash in a needed string column,
+        or with two breakdowns reading one source column, stays with
+        SQLite, as in _index_query; so does a query that leaves no key
+        column for the file ordinal."""
+        if not paths or mode == "0" or self.engine().name != "gpu":
+            return {}
+        from ..engine.plan import MAX_KEY
+        from ..index import columnar
+        if len(query.breakdowns) >= MAX_KEY:
+            return {}
+        srcs = [b.get("field", b["name"]) for b in query.breakdowns]
+        if len(set(srcs)) != len(srcs):
+            return {}
+        sidecars = [sc for sc in map(columnar.open_sidecar, paths)
+                    if sc is not None]
+        if not sidecars:
+            return {}
+        # a file that no metric serves fails in the per-file loop
+        groups, _errors = columnar.group_sidecars(sidecars, query)
+        if mode != "1":
+            total = sum(columnar.total_rows(m) for _f, m in groups)
+            if total < _env_columnar_rows():
+                return {}
+        from ..log import get_logger
+        log = get_logger().child("datasource-file")
+        served = {}
+        for found, members in groups:
+            needed = columnar.needed_columns(query, found)
+            if any(sc.column_info(f["id"], n).get("has_backslash")
+                   for sc, f in members for n in needed):
+                continue
+            launches, _rejected = columnar.merge_group(members, needed)
+            when = query.time_bounds_filter(found["datefield"]) \
+                if found["datefield"] else None
+            qfilter = None if found["ignore_filter"] else query.filter
+            filt = krill.filter_and(qfilter, when)
+            for mg in launches:
+                parts = self.engine().coded_query(
+                    query, filt, mg.params, mg.kinds, mg)
+                for sc, part in zip(mg.members, parts):
+                    served[sc.index_file] = part
+                columnar.STATS["sidecar_launches"] += 1
+                columnar.STATS["sidecar_files"] += len(mg.members)
+                log.info("index query served from sidecars",
+                         nfiles=len(mg.members), nrows=mg.nrows)
+        return served
 
     def _index_query(self, iq, query, mode="auto"):
         """K7: per-file index query, GPU-columnar when it pays.
@@ -318,10 +391,9 @@ class FileDatasource(object):
         qfilter = None if table["ignore_filter"] else query.filter
         filt = krill.filter_and(qfilter, when)
 
+        from ..index.query import column_kinds
         params = table["params"]
-        kinds = "".join(
-            "n" if ("aggr" in p or "date" in p) else "s"
-            for p in params)
+        kinds = column_kinds(params)
         sql = "SELECT %s from %s" % (
             ", ".join([sqlite3_escape(p["name"]) for p in params]
                       + ["value"]), table["table"])
@@ -391,12 +463,32 @@ def _env_rows_threshold():
         return float("inf")
 
 
+COLUMNAR_ROWS_DEFAULT = 500000
+
+
+def _env_columnar_rows():
+    """Total sidecar rows from which auto mode takes the columnar
+    sidecar path (DRAGNET_INDEX_COLUMNAR_ROWS).  The default is the
+    crossover measured in profiles/r07_columnar_index.md: the smallest
+    measured size at which the path's median beat SQLite's by more
+    than the spread in every run (at 50k rows it won too, but by less
+    than one run's spread)."""
+    v = os.environ.get("DRAGNET_INDEX_COLUMNAR_ROWS")
+    if v is None:
+        return COLUMNAR_ROWS_DEFAULT
+    try:
+        return int(v)
+    except ValueError:
+        return float("inf")
+
+
 def find_files(roots, counters=None):
     from ..fsfind import find_files as ff
     return ff(roots, counters=counters)
 
 
-def write_index(index_path, metrics, interval, points, partition=None):
+def write_index(index_path, metrics, interval, points, partition=None,
+                columnar=None):
     """Route aggregated points into per-interval IndexSinks; atomic
     rename on flush.  Returns ALL index file paths of the tree.
 
@@ -406,7 +498,19 @@ def write_index(index_path, metrics, interval, points, partition=None):
     materializes only the files it owns (disjoint parallel writes,
     reference reduce semantics lib/datasource-manta.js:334-350 spread
     across ranks).  The returned list still names the whole tree.
+
+    columnar: also write a columnar sidecar (index/columnar.py) beside
+    every file materialized here; None takes DRAGNET_INDEX_COLUMNAR=1.
     """
+    from ..index import columnar as mod_columnar
+    if columnar is None:
+        columnar = mod_columnar.enabled_by_env()
+
+    def flush(sink):
+        sink.flush()
+        if columnar:
+            mod_columnar.write_sidecar(sink.filename)
+
     from ..log import get_logger
     _log = get_logger().child("datasource-file")
     _log.info("writing index", index_path=index_path,
@@ -417,7 +521,7 @@ def write_index(index_path, metrics, interval, points, partition=None):
         sink = IndexSink(os.path.join(index_path, "all"), metrics)
         for p in points:
             sink.write_point(p)
-        sink.flush()
+        flush(sink)
         return [sink.filename]
 
     prefixlen, suffix, subdir, _pat, _step = INTERVALS[interval]
@@ -440,5 +544,5 @@ def write_index(index_path, metrics, interval, points, partition=None):
                          config={"dn_start": start})
         for p in buckets[name]:
             sink.write_point(p)
-        sink.flush()
+        flush(sink)
     return written

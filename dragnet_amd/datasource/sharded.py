@@ -109,13 +109,14 @@ class ShardedDatasource(FileDatasource):
                           [p for p, _ in files])
 
     def build(self, metrics, interval="day", after_ms=None,
-              before_ms=None, dry_run=False):
+              before_ms=None, dry_run=False, columnar=None):
         """Distributed build: every rank scans its shard (the map
         phase); the dense RCCL merge gives EVERY rank the full
         aggregate, so the reduce phase — materializing the index
         tree — is partitioned by interval bucket across ranks
         (disjoint files written in parallel; rank 0 returns the full
-        tree listing)."""
+        tree listing).  Each rank writes the columnar sidecars
+        (`columnar`, FileDatasource.build) of the files it owns."""
         from .file import write_index
         if not self.ds.index_path:
             raise ValueError(
@@ -133,7 +134,8 @@ class ShardedDatasource(FileDatasource):
                 points.append(p)
         partition = (self.rank, self.world) if self.world > 1 else None
         written = write_index(self.ds.index_path, metrics, interval,
-                              points, partition=partition)
+                              points, partition=partition,
+                              columnar=columnar)
         if self.dist is not None:
             self.dist.barrier()  # all files in place before any return
         return None if result.nonroot else written

@@ -56,10 +56,11 @@ class FindCounters(object):
         ]
 
 
-def find_files(roots, counters=None, warn=None):
+def find_files(roots, counters=None, warn=None, ignore=None):
     """Yield (path, stat) for every regular file / char device under each
     root, depth-first in sorted order.  `warn` is called with (path,
-    message) for stat failures."""
+    message) for stat failures.  Directory entries whose NAME `ignore`
+    accepts are passed over unseen: neither stat'ed nor counted."""
     counters = counters if counters is not None else FindCounters()
     for root in roots:
         counters.nstarts += 1
@@ -83,6 +84,8 @@ def find_files(roots, counters=None, warn=None):
                         warn(path, str(e))
                     continue
                 for name in entries:
+                    if ignore is not None and ignore(name):
+                        continue
                     stack.append(os.path.join(path, name))
             elif _stat.S_ISREG(mode) or _stat.S_ISCHR(mode):
                 if _stat.S_ISREG(mode):
@@ -95,7 +98,7 @@ def find_files(roots, counters=None, warn=None):
 
 
 def find_data_files(root, timeformat=None, after_ms=None, before_ms=None,
-                    counters=None, warn=None):
+                    counters=None, warn=None, ignore=None):
     """Enumerate the files a scan should read.
 
     With a timeformat and both time bounds, expand root/timeformat over
@@ -115,5 +118,6 @@ def find_data_files(root, timeformat=None, after_ms=None, before_ms=None,
             # 24 (tst.index_fileset.sh.out).
             n = len(pats)
             counters.npathenum = n + 1 if n < 16 else n
-        return find_files(pats, counters=counters, warn=warn)
-    return find_files([root], counters=counters, warn=warn)
+        return find_files(pats, counters=counters, warn=warn,
+                          ignore=ignore)
+    return find_files([root], counters=counters, warn=warn, ignore=ignore)

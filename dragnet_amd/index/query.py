@@ -39,67 +39,19 @@ class IndexQuerier(object):
             raise IndexError_("reading dragnet_config: %s" % e)
         for r in rows:
             self.config[r["key"]] = r["value"]
-        version = self.config.get("version")
-        if version is None:
-            raise IndexError_('index missing dragnet "version"')
-        if not str(version).startswith("2."):
-            raise IndexError_('unsupported index version: "%s"' % version)
+        check_version(self.config)
 
         rows = self.db.execute(
             "SELECT * FROM dragnet_metrics ORDER BY id").fetchall()
         for r in rows:
-            filt = json.loads(r["filter"]) if r["filter"] is not None \
-                else None
-            params = json.loads(r["params"]) if r["params"] is not None \
-                else []
-            self.metrics.append({
-                "id": r["id"],
-                "label": r["label"],
-                "filter": filt,
-                "filter_raw": r["filter"],
-                "params": params,
-            })
+            self.metrics.append(metric_entry(
+                r["id"], r["label"], r["filter"], r["params"]))
 
     def find_metric(self, query):
         """Pick the first metric that can serve this query; returns
         {datefield, table, ignore_filter, params} or raises IndexError_.
         """
-        filter_raw = None
-        if query.filter is not None:
-            filter_raw = json.dumps(query.filter, separators=(",", ":"))
-
-        for met in self.metrics:
-            datefield = None
-            if met["filter"] is not None:
-                if query.filter is None:
-                    continue
-                # exact-match only (a metric whose filter is a superset
-                # is conservatively skipped; same as the reference)
-                if _norm_json(met["filter_raw"]) != filter_raw:
-                    continue
-
-            if query.before_ms is not None or query.after_ms is not None:
-                dates = [p for p in met["params"] if "date" in p]
-                if not dates:
-                    continue
-                datefield = dates[0]["name"]
-
-            fields_needed = set()
-            if query.filter is not None and met["filter"] is None:
-                fields_needed.update(
-                    krill.create_predicate(query.filter).fields())
-            for b in query.breakdowns:
-                fields_needed.add(b["name"])
-            fields_have = set(p["name"] for p in met["params"])
-
-            if fields_needed <= fields_have:
-                return {
-                    "datefield": datefield,
-                    "table": "dragnet_index_%d" % met["id"],
-                    "ignore_filter": met["filter"] is not None,
-                    "params": met["params"],
-                }
-        raise IndexError_("no metrics available to serve query")
+        return find_metric(self.metrics, query)
 
     def run(self, query):
         """Execute the query against this index; returns an Aggregator
@@ -142,6 +94,80 @@ class IndexQuerier(object):
             if col in keys:
                 fields[b["name"]] = row[col]
         return {"fields": fields, "value": value}
+
+
+def check_version(config):
+    """Validate an index file's dragnet_config rows (version ~2)."""
+    version = config.get("version")
+    if version is None:
+        raise IndexError_('index missing dragnet "version"')
+    if not str(version).startswith("2."):
+        raise IndexError_('unsupported index version: "%s"' % version)
+
+
+def metric_entry(mid, label, filter_raw, params_raw):
+    """One dragnet_metrics row as IndexQuerier.metrics holds it."""
+    return {
+        "id": mid,
+        "label": label,
+        "filter": json.loads(filter_raw) if filter_raw is not None
+        else None,
+        "filter_raw": filter_raw,
+        "params": json.loads(params_raw) if params_raw is not None
+        else [],
+    }
+
+
+def column_kinds(params):
+    """How a metric table's columns are read as typed columns
+    (_csink.read_columns): 'n' numeric for aggregated and date params,
+    's' string for the rest."""
+    return "".join("n" if ("aggr" in p or "date" in p) else "s"
+                   for p in params)
+
+
+def find_metric(metrics, query):
+    """Pick the first of an index file's metrics (IndexQuerier.metrics
+    entries; no open database needed) that can serve this query; returns
+    {datefield, table, ignore_filter, params} or raises IndexError_.
+    """
+    filter_raw = None
+    if query.filter is not None:
+        filter_raw = json.dumps(query.filter, separators=(",", ":"))
+
+    for met in metrics:
+        datefield = None
+        if met["filter"] is not None:
+            if query.filter is None:
+                continue
+            # exact-match only (a metric whose filter is a superset
+            # is conservatively skipped; same as the reference)
+            if _norm_json(met["filter_raw"]) != filter_raw:
+                continue
+
+        if query.before_ms is not None or query.after_ms is not None:
+            dates = [p for p in met["params"] if "date" in p]
+            if not dates:
+                continue
+            datefield = dates[0]["name"]
+
+        fields_needed = set()
+        if query.filter is not None and met["filter"] is None:
+            fields_needed.update(
+                krill.create_predicate(query.filter).fields())
+        for b in query.breakdowns:
+            fields_needed.add(b["name"])
+        fields_have = set(p["name"] for p in met["params"])
+
+        if fields_needed <= fields_have:
+            return {
+                "datefield": datefield,
+                "id": met["id"],
+                "table": "dragnet_index_%d" % met["id"],
+                "ignore_filter": met["filter"] is not None,
+                "params": met["params"],
+            }
+    raise IndexError_("no metrics available to serve query")
 
 
 def _norm_json(raw):

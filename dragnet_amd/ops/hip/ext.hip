@@ -119,7 +119,8 @@ void newline_index(torch::Tensor data, int64_t start, int64_t n,
 }
 
 // Columnar index-query (K7): build the per-slot column descriptor
-// array (CPU bytes; caller copies to GPU).
+// array (CPU bytes; caller copies to GPU).  Kind 3 (a dictionary-coded
+// string column, scan_coded.h) passes its codes as soffs[f].
 torch::Tensor col_descs_host(std::vector<int64_t> kinds,
                              std::vector<torch::Tensor> nums,
                              std::vector<torch::Tensor> soffs,
@@ -132,8 +133,9 @@ torch::Tensor col_descs_host(std::vector<int64_t> kinds,
     d[f].kind = (int32_t)kinds[f];
     d[f].num = kinds[f] == 1 ? (const double*)nums[f].data_ptr()
                              : nullptr;
-    d[f].soff = kinds[f] == 2 ? (const uint32_t*)soffs[f].data_ptr()
-                              : nullptr;
+    d[f].soff = (kinds[f] == 2 || kinds[f] == COL_CODED)
+                    ? (const uint32_t*)soffs[f].data_ptr()
+                    : nullptr;
     d[f].slen = kinds[f] == 2 ? (const uint32_t*)slens[f].data_ptr()
                               : nullptr;
   }
@@ -300,12 +302,7 @@ class ScanState {
     A.values = (const double*)values.data_ptr();
     A.blob = (const uint8_t*)blob.data_ptr();
     A.cols = (const ColDesc*)col_descs.data_ptr();
-    A.P = args_.P;  // columns are pre-extracted: no key sigs, synthetics
-    A.P.sig_bloom = 0;
-    A.P.fields_parent_sig = 0;
-    A.P.ns = 0;
-    A.P.value_slot = -1;
-    A.P.fields_slot = -1;
+    A.P = column_plan();
     A.tables = args_.tables;
     A.sdict = args_.sdict;
     A.ndict = args_.ndict;
@@ -316,6 +313,71 @@ class ScanState {
     if (blocks == 0) return;
     launch("columnar_query", columnar_query_kernel, dim3(blocks),
            dim3(BLOCK), lds, A);
+  }
+
+  // Dictionary-coded index query (scan_coded.h) over the merged
+  // sidecar columns of a launch group: interns the launch dictionary
+  // (dict_blob, doff, dlen) into the state's StrDict, then evaluates
+  // the query over every row, on the current stream.  col_descs
+  // (col_descs_host, on device; kinds 0, 1 and 3) holds raw pointers
+  // into `columns`; seg_start is uint32 [nfiles + 1] row offsets, and
+  // the plan's last breakdown is the reserved file column.  The caller
+  // has validated codes < ndict and every doff + dlen within dict_blob.
+  // The state keeps every input referenced until its next columnar or
+  // coded call.
+  void coded_query(torch::Tensor col_descs, torch::Tensor dict_blob,
+                   torch::Tensor doff, torch::Tensor dlen,
+                   torch::Tensor seg_start, torch::Tensor values,
+                   int64_t nrows, std::vector<torch::Tensor> columns) {
+    for (auto* t : {&col_descs, &dict_blob, &doff, &dlen, &seg_start,
+                    &values})
+      CHECK_GPU(*t);
+    for (auto& t : columns) {
+      CHECK_GPU(t);
+      TORCH_CHECK(t.numel() >= nrows, "column shorter than nrows");
+    }
+    const PlanView& P = args_.P;
+    TORCH_CHECK(nrows >= 0 && nrows < (int64_t)0xFFFFFFFFll,
+                "coded query: row count exceeds 32 bits");
+    TORCH_CHECK(values.numel() >= nrows, "values shorter than nrows");
+    TORCH_CHECK(col_descs.numel() == (int64_t)(P.nf * sizeof(ColDesc)),
+                "col_descs does not match the plan's field count");
+    TORCH_CHECK(doff.numel() == dlen.numel(), "doff / dlen differ");
+    TORCH_CHECK(doff.numel() < (int64_t)0xFFFFFFFFll, "dictionary too big");
+    TORCH_CHECK(seg_start.numel() >= 2 &&
+                    seg_start.numel() - 1 < (int64_t)ORD_BIAS,
+                "seg_start needs nfiles + 1 entries");
+    auto code2id = zeros({std::max<int64_t>(doff.numel(), 1)}, I32);
+    col_inputs_ = std::move(columns);
+    col_inputs_.insert(col_inputs_.end(), {col_descs, dict_blob, doff, dlen,
+                                           seg_start, values, code2id});
+    CodedArgs A;
+    A.nrows = (uint32_t)nrows;
+    A.ndict = (uint32_t)doff.numel();
+    A.nfiles = (uint32_t)(seg_start.numel() - 1);
+    A.values = (const double*)values.data_ptr();
+    A.blob = (const uint8_t*)dict_blob.data_ptr();
+    A.doff = (const uint32_t*)doff.data_ptr();
+    A.dlen = (const uint32_t*)dlen.data_ptr();
+    A.code2id = (const uint32_t*)code2id.data_ptr();
+    A.seg_start = (const uint32_t*)seg_start.data_ptr();
+    A.cols = (const ColDesc*)col_descs.data_ptr();
+    A.P = column_plan();
+    A.tables = args_.tables;
+    A.sdict = args_.sdict;
+    A.ndict_num = args_.ndict;
+    A.counters = args_.counters;
+    size_t lds = lds_bytes(A.P.nf, A.P.nm, 0, true);
+    TORCH_CHECK(lds <= LDS_MAX, "coded plan needs too much LDS");
+    if (A.ndict > 0)
+      launch("dict_intern", dict_intern_kernel,
+             dim3((A.ndict + 255) / 256), dim3(256), 0, A.sdict, A.blob,
+             A.doff, A.dlen, A.ndict, (uint32_t*)code2id.data_ptr(),
+             overflow_ptr());
+    uint32_t blocks = grid_for((uint64_t)nrows);
+    if (blocks == 0) return;
+    launch("coded_query", coded_query_kernel, dim3(blocks), dim3(BLOCK),
+           lds, A);
   }
 
   // One-call zeroing of all scan state: a streaming step otherwise
@@ -520,6 +582,18 @@ class ScanState {
     }
   }
 
+  // The plan as the column kernels see it: columns are pre-extracted,
+  // so there are no key sigs and no synthetics.
+  PlanView column_plan() const {
+    PlanView P = args_.P;
+    P.sig_bloom = 0;
+    P.fields_parent_sig = 0;
+    P.ns = 0;
+    P.value_slot = -1;
+    P.fields_slot = -1;
+    return P;
+  }
+
   unsigned long long* overflow_ptr() {
     return (unsigned long long*)counters_.data_ptr() + C_OVERFLOW;
   }
@@ -603,7 +677,7 @@ class ScanState {
   // growth replaces it), owned_ for the plan's, which only the
   // descriptors point at
   std::vector<torch::Tensor> states_, keys_, counts_, partials_, owned_;
-  std::vector<torch::Tensor> col_inputs_;  // last columnar_query's inputs
+  std::vector<torch::Tensor> col_inputs_;  // last columnar / coded inputs
   torch::Tensor sd_state_, sd_hash_, sd_id_, sd_off_, sd_len_;
   torch::Tensor sd_data_, sd_used_, sd_next_;
   torch::Tensor nd_state_, nd_bits_, nd_id_, nd_next_;
@@ -644,6 +718,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::arg("col_descs"), py::arg("blob"), py::arg("values"),
            py::arg("nrows"), py::arg("columns"),
            "K7: query over uploaded index columns")
+      .def("coded_query", &dn::ScanState::coded_query,
+           py::arg("col_descs"), py::arg("dict_blob"), py::arg("doff"),
+           py::arg("dlen"), py::arg("seg_start"), py::arg("values"),
+           py::arg("nrows"), py::arg("keep"),
+           "query over merged dictionary-coded sidecar columns")
       .def("reset", &dn::ScanState::reset)
       .def("extract_all", &dn::ScanState::extract_all)
       .def("occupancy", &dn::ScanState::occupancy,

@@ -17,7 +17,8 @@
 //
 // Layers (docs/DESIGN.md): scan_text.h, scan_record.h (record semantics,
 // host-compilable too), scan_tables.h (device only), the kernels here,
-// scan_rehash.h (device only: table growth between launches).
+// scan_rehash.h (device only: table growth between launches),
+// scan_coded.h (device only: the dictionary-coded index query).
 
 #include "common.h"
 #include <hip/hip_runtime.h>
@@ -699,5 +700,9 @@ __global__ void extract_numdict_kernel(NumDict D, double* out_vals,
 // in-place table growth (the rehash kernels); last, so the kernels
 // above keep their place in the module
 #include "scan_rehash.h"
+
+// dictionary-coded index query over columnar sidecars (uses ColDesc
+// above); after everything else, for the same reason
+#include "scan_coded.h"
 
 }  // extern "C++"
