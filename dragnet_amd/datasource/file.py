@@ -317,18 +317,15 @@ class FileDatasource(object):
         Only a GPU engine reads sidecars.  "1" takes this path wherever
         sidecars are usable; "auto" only from
         DRAGNET_INDEX_COLUMNAR_ROWS sidecar rows up (counted from the
-        headers).  A group with a backslash in a needed string column,
-        or with two breakdowns reading one source column, stays with
-        SQLite, as in _index_query; so does a query that leaves no key
-        column for the file ordinal."""
+        headers).  A group with a backslash in a needed string column
+        stays with SQLite, as in _index_query; so does a query that the
+        column kernels cannot plan (_shares_source_column), or that
+        leaves no key column for the file ordinal."""
         if not paths or mode == "0" or self.engine().name != "gpu":
             return {}
         from ..engine.plan import MAX_KEY
         from ..index import columnar
-        if len(query.breakdowns) >= MAX_KEY:
-            return {}
-        srcs = [b.get("field", b["name"]) for b in query.breakdowns]
-        if len(set(srcs)) != len(srcs):
+        if len(query.breakdowns) >= MAX_KEY or _shares_source_column(query):
             return {}
         sidecars = [sc for sc in map(columnar.open_sidecar, paths)
                     if sc is not None]
@@ -349,10 +346,7 @@ class FileDatasource(object):
                    for sc, f in members for n in needed):
                 continue
             launches, _rejected = columnar.merge_group(members, needed)
-            when = query.time_bounds_filter(found["datefield"]) \
-                if found["datefield"] else None
-            qfilter = None if found["ignore_filter"] else query.filter
-            filt = krill.filter_and(qfilter, when)
+            filt = _column_filter(query, found)
             for mg in launches:
                 parts = self.engine().coded_query(
                     query, filt, mg.params, mg.kinds, mg)
@@ -384,13 +378,11 @@ class FileDatasource(object):
             if n < _env_rows_threshold():
                 return iq.run(query)
 
+        if _shares_source_column(query):
+            return iq.run(query)
+
         from ..index import _csink
         from ..index.sink import sqlite3_escape
-        when = query.time_bounds_filter(table["datefield"]) \
-            if table["datefield"] else None
-        qfilter = None if table["ignore_filter"] else query.filter
-        filt = krill.filter_and(qfilter, when)
-
         from ..index.query import column_kinds
         params = table["params"]
         kinds = column_kinds(params)
@@ -404,13 +396,8 @@ class FileDatasource(object):
         for k, c in zip(kinds, cols):
             if k == "s" and b"\\" in c[0]:
                 return iq.run(query)
-        # two breakdowns reading the same source column can't share a
-        # kernel-plan name — rare; served by SQLite
-        srcs = [b.get("field", b["name"]) for b in query.breakdowns]
-        if len(set(srcs)) != len(srcs):
-            return iq.run(query)
-        return self.engine().columnar_query(query, filt, params,
-                                            kinds, cols, vals)
+        return self.engine().columnar_query(
+            query, _column_filter(query, table), params, kinds, cols, vals)
 
     def index_read_points(self, metrics, interval="day"):
         """Emit every stored row of every index file as tagged points
@@ -444,6 +431,23 @@ class FileDatasource(object):
 def _esc(c):
     from ..index.sink import sqlite3_escape
     return sqlite3_escape(c)
+
+
+def _column_filter(query, found):
+    """The krill filter a column query applies to the rows of a found
+    metric: the query's own, unless the metric was built with it, and
+    the time bounds where the metric has a date field."""
+    when = query.time_bounds_filter(found["datefield"]) \
+        if found["datefield"] else None
+    qfilter = None if found["ignore_filter"] else query.filter
+    return krill.filter_and(qfilter, when)
+
+
+def _shares_source_column(query):
+    """Two breakdowns reading the same source column can't share a
+    kernel-plan name — rare; such a query is served by SQLite."""
+    srcs = [b.get("field", b["name"]) for b in query.breakdowns]
+    return len(set(srcs)) != len(srcs)
 
 
 def _env_rows_threshold():

@@ -11,6 +11,8 @@ downstream consumer (formatters, index sink, RCCL merge) is
 engine-agnostic.  File scans take their chunks from the host-only
 framer in engine/chunks.py.  The tables, dictionaries and counters
 belong to the extension's ScanState, which allocates and grows them.
+Index queries over stored columns (ops/hip/scan_columns.h) are driven
+from engine/colquery.py.
 
 Capacity handling: the hash tables and dictionaries are sized up front,
 as a first guess.  A scan of regular files restarts on overflow
@@ -44,6 +46,13 @@ def _env_int(name, default):
         return int(os.environ.get(name, default))
     except ValueError:
         return default
+
+
+def first_guess_slots():
+    """(aggregation, dictionary) table slots a scan or an index query
+    starts with; an overflow multiplies them."""
+    return (_env_int("DRAGNET_AGG_SLOTS", 1 << 20),
+            _env_int("DRAGNET_DICT_SLOTS", 1 << 20))
 
 
 def _is_regular(path):
@@ -88,8 +97,7 @@ class GpuEngine(object):
             queries, ds_filter=ds_filter, time_field=time_field,
             data_format=data_format)
 
-        agg_slots = _env_int("DRAGNET_AGG_SLOTS", 1 << 20)
-        dict_slots = _env_int("DRAGNET_DICT_SLOTS", 1 << 20)
+        agg_slots, dict_slots = first_guess_slots()
         dict_data = _env_int("DRAGNET_DICT_DATA_MB", 256) * 1024 * 1024
 
         # Input that cannot be read twice cannot restart: it scans once,
@@ -144,34 +152,6 @@ class GpuEngine(object):
                               gpu_stats=dict(nogrow, restarts=attempt))
         raise RuntimeError("aggregation tables overflowed after retries")
 
-    @staticmethod
-    def _column_plan(query, filt, extra=()):
-        """The kernel plan of an index query over stored columns
-        (columnar_query, coded_query); `extra` breakdowns follow the
-        query's own."""
-        from ..query import QueryConfig
-
-        # kernel plan: each breakdown reads the column keyed by its
-        # FIELD name — the reference's deserializeRow reads
-        # row[escape(field.field)] (lib/index-query.js:395-400), so a
-        # renamed date breakdown (field != name) reads a column that
-        # was never selected -> undefined -> dropped by the
-        # bucketizer.  Stored columns are keyed by NAME, so mapping
-        # the kernel slot by field reproduces exactly that; the
-        # caller's query does the date/bucket decode.
-        kq_bds = []
-        for b in query.breakdowns:
-            src = b.get("field", b["name"])
-            nb = {"name": src, "field": src}
-            if "aggr" in b:
-                nb["aggr"] = b["aggr"]
-                if "step" in b:
-                    nb["step"] = b["step"]
-            kq_bds.append(nb)
-        kq = QueryConfig(filter=None, breakdowns=kq_bds + list(extra),
-                         allow_reserved=True)
-        return planmod.compile_plan([kq], ds_filter=filt)
-
     def columnar_query(self, query, filt, params, kinds, cols, vals):
         """K7: evaluate `query` over one index metric's typed columns
         on-device (columnar_query_kernel) — no NDJSON round trip
@@ -186,73 +166,15 @@ class GpuEngine(object):
         cols:   per column f64 numpy array or (blob, offs, lens)
         vals:   f64 numpy array of row weights
         """
-        torch = self.torch
-        dev = self.device
-        cplan = self._column_plan(query, filt)
-
-        # slot -> column mapping; companion slots stay missing
-        by_name = {p["name"]: i for i, p in enumerate(params)}
-        nf = len(cplan.field_sigs)
-        slot_kinds = [0] * nf
-        keep = []  # column tensors the descriptor array points into
-        nums, soffs, slens = ([torch.empty(0)] * nf for _ in range(3))
-        blobs = []
-        bias = 0
-        biases = {}
-        for ci, c in enumerate(cols):
-            if kinds[ci] == "s":
-                biases[ci] = bias
-                blobs.append(c[0])
-                bias += len(c[0])
-        blob = b"".join(blobs) or b"\0"
-        blob_t = torch.from_numpy(
-            np.frombuffer(blob, dtype=np.uint8).copy()).to(dev)
-        nrows = int(vals.shape[0])
-        for si, (path, _raw) in enumerate(cplan.fields.paths):
-            ci = by_name.get(path)
-            if ci is None:
-                continue
-            if kinds[ci] == "n":
-                slot_kinds[si] = 1
-                t = torch.from_numpy(
-                    np.ascontiguousarray(cols[ci])).to(dev)
-                nums[si] = t
-                keep.append(t)
-            else:
-                slot_kinds[si] = 2
-                off = cols[ci][1].astype(np.uint32) + \
-                    np.uint32(biases[ci])
-                to = torch.from_numpy(off.view(np.int32)).to(dev)
-                tl = torch.from_numpy(
-                    cols[ci][2].view(np.int32).copy()).to(dev)
-                soffs[si] = to
-                slens[si] = tl
-                keep.extend([to, tl])
-        vals_t = torch.from_numpy(
-            np.ascontiguousarray(vals)).to(dev)
-        descs = self.ops.col_descs_host(slot_kinds, nums, soffs,
-                                        slens).to(dev)
-
-        agg_slots = _env_int("DRAGNET_AGG_SLOTS", 1 << 20)
-        dict_slots = _env_int("DRAGNET_DICT_SLOTS", 1 << 20)
-        dict_cap = max(len(blob) * 2 + (1 << 20), 8 << 20)
-        for _ in range(2):
-            ctx = _ScanContext(self, cplan, agg_slots, dict_slots,
-                               dict_cap, dense=False)
-            ctx.state.columnar_query(descs, blob_t, vals_t, nrows, keep)
-            aggs, _stages = ctx.finalize([query])
-            if not ctx.overflowed():
-                return aggs[0]
-            agg_slots *= 8
-            dict_slots *= 8
-            dict_cap *= 4
-        raise RuntimeError("columnar query overflowed after retry")
+        from . import colquery
+        return colquery.columnar_query(self, query, filt, params, kinds,
+                                       cols, vals)
 
     def coded_query(self, query, filt, params, kinds, merged,
                     timings=None):
         """Evaluate `query` over the merged, dictionary-coded sidecar
         columns of a whole launch group in one pass (dict_intern_kernel
-        + coded_query_kernel, ops/hip/scan_coded.h).
+        + coded_query_kernel, ops/hip/scan_columns.h).
 
         query, filt, params, kinds: as columnar_query takes them
         merged: index.columnar.Merged — the needed columns of the
@@ -266,94 +188,9 @@ class GpuEngine(object):
         Returns one Aggregator per file of the group, in order: that
         file's partial result, as its own SQLite GROUP BY would give.
         """
-        torch = self.torch
-        dev = self.device
-        from ..index.columnar import FILE_COLUMN
-        from ..points import Aggregator
-        from ..query import QueryConfig
-        import time
-        clock = [time.perf_counter()]
-
-        def mark(phase):
-            if timings is None:
-                return
-            torch.cuda.synchronize(dev)
-            now = time.perf_counter()
-            timings[phase] = timings.get(phase, 0.0) + now - clock[0]
-            clock[0] = now
-
-        # the file ordinal rides in a reserved trailing breakdown; the
-        # decode query carries it too, so decode needs no change
-        file_bd = {"name": FILE_COLUMN, "field": FILE_COLUMN,
-                   "aggr": "lquantize", "step": 1}
-        cplan = self._column_plan(query, filt, extra=[file_bd])
-        dq = QueryConfig(
-            filter=None,
-            breakdowns=[dict(b) for b in query.breakdowns] + [file_bd],
-            allow_reserved=True)
-
-        def up(arr, view=None):
-            arr = np.ascontiguousarray(arr)
-            return torch.from_numpy(
-                arr.view(view) if view else arr).to(dev)
-
-        by_name = {p["name"]: i for i, p in enumerate(params)}
-        nf = len(cplan.field_sigs)
-        slot_kinds = [0] * nf
-        keep = []
-        nums, codes = ([torch.empty(0)] * nf for _ in range(2))
-        for si, (path, _raw) in enumerate(cplan.fields.paths):
-            ci = by_name.get(path)
-            if ci is None:
-                continue  # (the file column's slot among them)
-            if kinds[ci] == "n":
-                slot_kinds[si] = 1
-                nums[si] = up(merged.nums[path])
-                keep.append(nums[si])
-            else:
-                slot_kinds[si] = 3
-                codes[si] = up(merged.codes[path], np.int32)
-                keep.append(codes[si])
-        blob, doff, dlen = merged.dictionary()
-        # 16 bytes of slack: the text layer reads 8-byte words
-        blob_t = up(np.frombuffer(blob + b"\0" * 16, dtype=np.uint8).copy())
-        doff_t = up(doff, np.int32)
-        dlen_t = up(dlen, np.int32)
-        seg_t = up(merged.seg_start, np.int32)
-        vals_t = up(merged.values)
-        nrows = merged.nrows
-        descs = self.ops.col_descs_host(slot_kinds, nums, codes,
-                                        codes).to(dev)
-        mark("h2d")
-
-        agg_slots = _env_int("DRAGNET_AGG_SLOTS", 1 << 20)
-        dict_slots = _env_int("DRAGNET_DICT_SLOTS", 1 << 20)
-        dict_cap = max(len(blob) * 2 + 8 * len(doff) + (1 << 20), 8 << 20)
-        for _ in range(4):
-            ctx = _ScanContext(self, cplan, agg_slots, dict_slots,
-                               min(dict_cap, 0xFFFFFFFF), dense=False)
-            ctx.state.coded_query(descs, blob_t, doff_t, dlen_t, seg_t,
-                                  vals_t, nrows, keep)
-            mark("kernels")
-            aggs, _stages = ctx.finalize([dq])
-            if not ctx.overflowed():
-                break
-            self.coded_stats["retries"] += 1
-            agg_slots *= 8
-            dict_slots *= 8
-            dict_cap *= 4
-        else:
-            raise RuntimeError("coded query overflowed after retries")
-
-        self.coded_stats["launches"] += 1
-
-        # split by file ordinal and strip it
-        parts = [Aggregator(query) for _ in merged.members]
-        for key, v in aggs[0].table.items():
-            t = parts[key[-1]].table
-            t[key[:-1]] = t.get(key[:-1], 0) + v
-        mark("decode")
-        return parts
+        from . import colquery
+        return colquery.coded_query(self, query, filt, params, kinds,
+                                    merged, timings)
 
 
 class _ScanContext(object):

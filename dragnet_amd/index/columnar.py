@@ -1,8 +1,8 @@
 """
 Columnar index sidecars: a dictionary-coded cache of an index file's
 metric tables, and the host-side merge of a tree's sidecars into one
-launch for the GPU engine (GpuEngine.coded_query).  numpy only: neither
-torch nor a GPU is needed here.
+launch for the GPU engine (GpuEngine.coded_query, engine/colquery.py).
+numpy only: neither torch nor a GPU is needed here.
 
 A sidecar for index file F is F.dncol.  It holds exactly what
 _csink.read_columns returns for each metric table of F — built from the

@@ -119,8 +119,8 @@ void newline_index(torch::Tensor data, int64_t start, int64_t n,
 }
 
 // Columnar index-query (K7): build the per-slot column descriptor
-// array (CPU bytes; caller copies to GPU).  Kind 3 (a dictionary-coded
-// string column, scan_coded.h) passes its codes as soffs[f].
+// array (CPU bytes; caller copies to GPU).  Kinds as scan_columns.h
+// has them; a dictionary-coded column passes its codes as soffs[f].
 torch::Tensor col_descs_host(std::vector<int64_t> kinds,
                              std::vector<torch::Tensor> nums,
                              std::vector<torch::Tensor> soffs,
@@ -131,13 +131,13 @@ torch::Tensor col_descs_host(std::vector<int64_t> kinds,
   ColDesc* d = (ColDesc*)out.data_ptr();
   for (int f = 0; f < nf; f++) {
     d[f].kind = (int32_t)kinds[f];
-    d[f].num = kinds[f] == 1 ? (const double*)nums[f].data_ptr()
-                             : nullptr;
-    d[f].soff = (kinds[f] == 2 || kinds[f] == COL_CODED)
+    d[f].num = kinds[f] == COL_NUM ? (const double*)nums[f].data_ptr()
+                                   : nullptr;
+    d[f].soff = (kinds[f] == COL_STR || kinds[f] == COL_CODED)
                     ? (const uint32_t*)soffs[f].data_ptr()
                     : nullptr;
-    d[f].slen = kinds[f] == 2 ? (const uint32_t*)slens[f].data_ptr()
-                              : nullptr;
+    d[f].slen = kinds[f] == COL_STR ? (const uint32_t*)slens[f].data_ptr()
+                                    : nullptr;
   }
   return out;
 }
@@ -181,7 +181,7 @@ class ScanState {
       return owned_.back().data_ptr();
     };
     PlanView& P = args_.P;
-    // the ONE place a PlanView is filled (columnar_query adjusts a copy)
+    // the ONE place a PlanView is filled (column_plan adjusts a copy)
     P.field_sigs = (const uint64_t*)ptr(plan, "field_sigs");
     P.nf = (int)owned_.back().numel();
     P.comp_slot = (const int32_t*)ptr(plan, "comp_slot");
@@ -286,98 +286,55 @@ class ScanState {
 
   // Columnar index-query (K7) over uploaded index columns.  col_descs
   // (col_descs_host, on device) holds raw pointers into `columns`; the
-  // state keeps every input referenced until its next columnar call,
-  // so none can be freed before the launch is enqueued.
+  // state keeps every input referenced until its next columnar or coded
+  // call, so none can be freed before the launch is enqueued.
   void columnar_query(torch::Tensor col_descs, torch::Tensor blob,
                       torch::Tensor values, int64_t nrows,
                       std::vector<torch::Tensor> columns) {
-    CHECK_GPU(col_descs);
-    CHECK_GPU(blob);
-    CHECK_GPU(values);
-    for (auto& t : columns) CHECK_GPU(t);
-    col_inputs_ = std::move(columns);
-    col_inputs_.insert(col_inputs_.end(), {col_descs, blob, values});
-    ColArgs A;
-    A.nrows = (uint32_t)nrows;
-    A.values = (const double*)values.data_ptr();
-    A.blob = (const uint8_t*)blob.data_ptr();
-    A.cols = (const ColDesc*)col_descs.data_ptr();
-    A.P = column_plan();
-    A.tables = args_.tables;
-    A.sdict = args_.sdict;
-    A.ndict = args_.ndict;
-    A.counters = args_.counters;
-    size_t lds = lds_bytes(A.P.nf, A.P.nm, 0, true);
-    TORCH_CHECK(lds <= LDS_MAX, "columnar plan needs too much LDS");
-    uint32_t blocks = grid_for((uint64_t)nrows);
-    if (blocks == 0) return;
-    launch("columnar_query", columnar_query_kernel, dim3(blocks),
-           dim3(BLOCK), lds, A);
+    ColumnLaunch L = bind_columns("columnar", col_descs, blob, values,
+                                  nrows, std::move(columns));
+    if (L.blocks == 0) return;
+    launch("columnar_query", columnar_query_kernel, dim3(L.blocks),
+           dim3(BLOCK), L.lds, L.A);
   }
 
-  // Dictionary-coded index query (scan_coded.h) over the merged
-  // sidecar columns of a launch group: interns the launch dictionary
-  // (dict_blob, doff, dlen) into the state's StrDict, then evaluates
-  // the query over every row, on the current stream.  col_descs
-  // (col_descs_host, on device; kinds 0, 1 and 3) holds raw pointers
-  // into `columns`; seg_start is uint32 [nfiles + 1] row offsets, and
-  // the plan's last breakdown is the reserved file column.  The caller
-  // has validated codes < ndict and every doff + dlen within dict_blob.
-  // The state keeps every input referenced until its next columnar or
-  // coded call.
+  // Dictionary-coded index query over the merged sidecar columns of a
+  // launch group: interns the launch dictionary (dict_blob, doff, dlen)
+  // into the state's StrDict, then evaluates the query over every row,
+  // on the current stream.  col_descs holds kinds 0, 1 and 3; seg_start
+  // is uint32 [nfiles + 1] row offsets, and the plan's last breakdown is
+  // the reserved file column.  The caller has validated codes < ndict
+  // and every doff + dlen within dict_blob.
   void coded_query(torch::Tensor col_descs, torch::Tensor dict_blob,
                    torch::Tensor doff, torch::Tensor dlen,
                    torch::Tensor seg_start, torch::Tensor values,
                    int64_t nrows, std::vector<torch::Tensor> columns) {
-    for (auto* t : {&col_descs, &dict_blob, &doff, &dlen, &seg_start,
-                    &values})
-      CHECK_GPU(*t);
-    for (auto& t : columns) {
-      CHECK_GPU(t);
-      TORCH_CHECK(t.numel() >= nrows, "column shorter than nrows");
-    }
-    const PlanView& P = args_.P;
-    TORCH_CHECK(nrows >= 0 && nrows < (int64_t)0xFFFFFFFFll,
-                "coded query: row count exceeds 32 bits");
-    TORCH_CHECK(values.numel() >= nrows, "values shorter than nrows");
-    TORCH_CHECK(col_descs.numel() == (int64_t)(P.nf * sizeof(ColDesc)),
-                "col_descs does not match the plan's field count");
+    for (auto* t : {&doff, &dlen, &seg_start}) CHECK_GPU(*t);
     TORCH_CHECK(doff.numel() == dlen.numel(), "doff / dlen differ");
     TORCH_CHECK(doff.numel() < (int64_t)0xFFFFFFFFll, "dictionary too big");
     TORCH_CHECK(seg_start.numel() >= 2 &&
                     seg_start.numel() - 1 < (int64_t)ORD_BIAS,
                 "seg_start needs nfiles + 1 entries");
+    ColumnLaunch L = bind_columns("coded", col_descs, dict_blob, values,
+                                  nrows, std::move(columns));
     auto code2id = zeros({std::max<int64_t>(doff.numel(), 1)}, I32);
-    col_inputs_ = std::move(columns);
-    col_inputs_.insert(col_inputs_.end(), {col_descs, dict_blob, doff, dlen,
-                                           seg_start, values, code2id});
-    CodedArgs A;
-    A.nrows = (uint32_t)nrows;
-    A.ndict = (uint32_t)doff.numel();
-    A.nfiles = (uint32_t)(seg_start.numel() - 1);
-    A.values = (const double*)values.data_ptr();
-    A.blob = (const uint8_t*)dict_blob.data_ptr();
-    A.doff = (const uint32_t*)doff.data_ptr();
-    A.dlen = (const uint32_t*)dlen.data_ptr();
-    A.code2id = (const uint32_t*)code2id.data_ptr();
-    A.seg_start = (const uint32_t*)seg_start.data_ptr();
-    A.cols = (const ColDesc*)col_descs.data_ptr();
-    A.P = column_plan();
-    A.tables = args_.tables;
-    A.sdict = args_.sdict;
-    A.ndict_num = args_.ndict;
-    A.counters = args_.counters;
-    size_t lds = lds_bytes(A.P.nf, A.P.nm, 0, true);
-    TORCH_CHECK(lds <= LDS_MAX, "coded plan needs too much LDS");
-    if (A.ndict > 0)
+    col_inputs_.insert(col_inputs_.end(),
+                       {doff, dlen, seg_start, code2id});
+    CodedArgs X;
+    X.ndict = (uint32_t)doff.numel();
+    X.nfiles = (uint32_t)(seg_start.numel() - 1);
+    X.doff = (const uint32_t*)doff.data_ptr();
+    X.dlen = (const uint32_t*)dlen.data_ptr();
+    X.code2id = (const uint32_t*)code2id.data_ptr();
+    X.seg_start = (const uint32_t*)seg_start.data_ptr();
+    if (X.ndict > 0)
       launch("dict_intern", dict_intern_kernel,
-             dim3((A.ndict + 255) / 256), dim3(256), 0, A.sdict, A.blob,
-             A.doff, A.dlen, A.ndict, (uint32_t*)code2id.data_ptr(),
+             dim3((X.ndict + 255) / 256), dim3(256), 0, L.A.sdict, L.A.blob,
+             X.doff, X.dlen, X.ndict, (uint32_t*)code2id.data_ptr(),
              overflow_ptr());
-    uint32_t blocks = grid_for((uint64_t)nrows);
-    if (blocks == 0) return;
-    launch("coded_query", coded_query_kernel, dim3(blocks), dim3(BLOCK),
-           lds, A);
+    if (L.blocks == 0) return;
+    launch("coded_query", coded_query_kernel, dim3(L.blocks), dim3(BLOCK),
+           L.lds, L.A, X);
   }
 
   // One-call zeroing of all scan state: a streaming step otherwise
@@ -580,6 +537,48 @@ class ScanState {
                   new_size, ": device allocation failed (",
                   why.substr(0, why.find('\n')), ")");
     }
+  }
+
+  struct ColumnLaunch {
+    ColArgs A;
+    size_t lds;
+    uint32_t blocks;  // 0: no rows, nothing to launch
+  };
+
+  // What a column-query launch (scan_columns.h) takes whichever kernel
+  // runs it: checks the inputs against nrows and the plan, keeps them
+  // referenced in col_inputs_, and fills the arguments from args_.
+  ColumnLaunch bind_columns(const char* what, torch::Tensor col_descs,
+                            torch::Tensor blob, torch::Tensor values,
+                            int64_t nrows,
+                            std::vector<torch::Tensor> columns) {
+    for (auto* t : {&col_descs, &blob, &values}) CHECK_GPU(*t);
+    for (auto& t : columns) {
+      CHECK_GPU(t);
+      TORCH_CHECK(t.numel() >= nrows, "column shorter than nrows");
+    }
+    TORCH_CHECK(nrows >= 0 && nrows < (int64_t)0xFFFFFFFFll, what,
+                " query: row count exceeds 32 bits");
+    TORCH_CHECK(values.numel() >= nrows, "values shorter than nrows");
+    ColumnLaunch L;
+    ColArgs& A = L.A;
+    A.P = column_plan();
+    TORCH_CHECK(col_descs.numel() == (int64_t)(A.P.nf * sizeof(ColDesc)),
+                "col_descs does not match the plan's field count");
+    L.lds = lds_bytes(A.P.nf, A.P.nm, 0, true);
+    TORCH_CHECK(L.lds <= LDS_MAX, what, " plan needs too much LDS");
+    A.nrows = (uint32_t)nrows;
+    A.values = (const double*)values.data_ptr();
+    A.blob = (const uint8_t*)blob.data_ptr();
+    A.cols = (const ColDesc*)col_descs.data_ptr();
+    A.tables = args_.tables;
+    A.sdict = args_.sdict;
+    A.ndict = args_.ndict;
+    A.counters = args_.counters;
+    col_inputs_ = std::move(columns);
+    col_inputs_.insert(col_inputs_.end(), {col_descs, blob, values});
+    L.blocks = grid_for((uint64_t)nrows);
+    return L;
   }
 
   // The plan as the column kernels see it: columns are pre-extracted,

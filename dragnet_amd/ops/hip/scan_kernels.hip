@@ -18,7 +18,7 @@
 // Layers (docs/DESIGN.md): scan_text.h, scan_record.h (record semantics,
 // host-compilable too), scan_tables.h (device only), the kernels here,
 // scan_rehash.h (device only: table growth between launches),
-// scan_coded.h (device only: the dictionary-coded index query).
+// scan_columns.h (device only: the index queries over typed columns).
 
 #include "common.h"
 #include <hip/hip_runtime.h>
@@ -204,117 +204,6 @@ __global__ void newline_write_kernel(const uint8_t* data,
     }
     w_at += __shfl(incl, 63, 64);  // wave total
   }
-}
-
-// -------------------------------------------------------------------
-// Columnar index-query kernel (K7): evaluate a query directly over an
-// index table's typed columns (reference lib/index-query.js:303-338
-// runs SELECT ... WHERE pred GROUP BY; here the predicate + bucketize
-// + hash-aggregate run over uploaded columns — no NDJSON round trip).
-// Rows are weighted points: weight = the stored SUM(value).
-
-struct ColDesc {
-  int32_t kind;  // 0 = missing for every row, 1 = numeric, 2 = string
-  int32_t pad_;
-  const double* num;     // [nrows] (kind 1)
-  const uint32_t* soff;  // [nrows] into the shared blob (kind 2)
-  const uint32_t* slen;
-};
-
-struct ColArgs {
-  uint32_t nrows;
-  const double* values;  // [nrows] row weights
-  const uint8_t* blob;   // concatenated string payloads
-  const ColDesc* cols;   // [P.nf] per plan slot
-  PlanView P;
-  AggTable* tables;
-  StrDict sdict;
-  NumDict ndict;
-  unsigned long long* counters;
-};
-
-// 5 waves/SIMD is what this kernel compiles to (91 VGPRs); holding the
-// register allocator to it keeps the SGPR spill count at the level the
-// kernel had before it shared the aggregation tail (157 vs 163; at a
-// bound of 4 the allocator lands on 165).
-__launch_bounds__(BLOCK, 5)
-__global__ void columnar_query_kernel(ColArgs A) {
-  extern __shared__ __attribute__((aligned(16))) char smemc[];
-  const PlanView& P = A.P;
-  const int nf = P.nf;
-  const LdsLayout L(nf, P.nm, 0, false);
-  LdsCacheEntry* cache = reinterpret_cast<LdsCacheEntry*>(smemc + L.cache);
-  unsigned long long* lcnt =
-      reinterpret_cast<unsigned long long*>(smemc + L.lcnt);
-  const int NCNT = C_GLOBAL_N + P.nm * CM_N;
-  block_agg_init(cache, lcnt, NCNT);
-
-  FV fv;
-  fv.type = reinterpret_cast<uint8_t*>(smemc + L.fv_type);
-  fv.soff = reinterpret_cast<uint32_t*>(smemc + L.fv_soff);
-  fv.slen = reinterpret_cast<uint32_t*>(smemc + L.fv_slen);
-  fv.tid = threadIdx.x;
-  Bytes BV;
-  BV.mem = A.blob;
-  BV.bias = 0;
-
-  const uint32_t stride = gridDim.x * BLOCK;
-  for (uint32_t r = blockIdx.x * BLOCK + threadIdx.x; r < A.nrows;
-       r += stride) {
-    atomicAdd(&lcnt[C_LINES], 1ull);
-    atomicAdd(&lcnt[C_PARSED], 1ull);
-    for (int f = 0; f < nf; f++) {
-      const ColDesc& c = A.cols[f];
-      if (c.kind == 1)
-        fv.set(f, T_NUM, 0, 0, c.num[r]);
-      else if (c.kind == 2)
-        fv.set(f, T_STR, c.soff[r], c.slen[r], 0.0);
-      else
-        fv.set(f, T_MISSING, 0, 0, 0.0);
-    }
-    // program 0: the combined (query ∧ time-bounds) filter
-    {
-      int keep = eval_predicate(P, BV, fv, 0);
-      if (keep != 1) {
-        if (keep == -1) atomicAdd(&lcnt[C_DS_FAILEDEVAL], 1ull);
-        else atomicAdd(&lcnt[C_DS_FILTERED], 1ull);
-        continue;
-      }
-    }
-    double weight = A.values[r];
-    for (int m = 0; m < P.nm; m++) {
-      const int32_t* M = &P.metric_rows[m * 8];
-      unsigned long long* mc = &lcnt[C_GLOBAL_N + m * CM_N];
-      atomicAdd(&mc[CM_AGG_IN], 1ull);
-
-      uint32_t key[MAX_KEY];
-      int nk = M[1];
-      bool drop = false, overflow = false;
-      for (int bi = 0; bi < nk; bi++) {
-        const int32_t* B = &P.bd_rows[(M[2] + bi) * 4];
-        int slot = B[1];  // columnar plans use kind-0 refs only
-        uint32_t code;
-        if (!encode_key_col(A.sdict, A.ndict, BV, fv.get_type(slot),
-                            fv.get_num(slot), fv.get_soff(slot),
-                            fv.get_slen(slot), B[2],
-                            P.bd_steps[M[2] + bi], code, drop, overflow))
-          break;
-#pragma unroll
-        for (int kk = 0; kk < MAX_KEY; kk++)
-          if (kk == bi) key[kk] = code;
-      }
-      if (overflow) { atomicAdd(&lcnt[C_OVERFLOW], 1ull); continue; }
-      if (drop) { atomicAdd(&mc[CM_NONNUMERIC], 1ull); continue; }
-#pragma unroll
-      for (int k = 0; k < MAX_KEY; k++)
-        if (k >= nk) key[k] = 0;
-
-      lds_cache_add<8>(cache, A.tables, A.counters, lcnt, m, key, nk,
-                    agg_key_hash(m, key), weight);
-    }
-  }
-
-  block_agg_flush(cache, lcnt, NCNT, P, A.tables, A.counters);
 }
 
 // Device-side wave-transpose builder: scatter each (length-sorted)
@@ -701,8 +590,8 @@ __global__ void extract_numdict_kernel(NumDict D, double* out_vals,
 // above keep their place in the module
 #include "scan_rehash.h"
 
-// dictionary-coded index query over columnar sidecars (uses ColDesc
-// above); after everything else, for the same reason
-#include "scan_coded.h"
+// index queries over typed columns (K7 and the columnar sidecars);
+// after everything else, for the same reason
+#include "scan_columns.h"
 
 }  // extern "C++"

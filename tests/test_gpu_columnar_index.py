@@ -117,7 +117,7 @@ def hosts_of(k):
     return ["m"] + ["a%d" % j for j in range(k)] + ["z%d" % k]
 
 
-def write_file(path, k, nrows, host_of=None):
+def write_file(path, k, nrows, host_of=None, sidecar=True):
     sink = IndexSink(path, [METRIC])
     hosts = hosts_of(k)
     for i in range(nrows):
@@ -128,7 +128,8 @@ def write_file(path, k, nrows, host_of=None):
             "method": METHODS[(i + k) % 3],
             "lat": LATS[(i // 3 + k) % len(LATS)]}, "value": 1 + i % 4})
     sink.flush()
-    C.write_sidecar(path)
+    if sidecar:
+        C.write_sidecar(path)
 
 
 @pytest.fixture(scope="module")
@@ -157,6 +158,17 @@ def seg_tree(tmp_path_factory):
     return idx
 
 
+@pytest.fixture(scope="module")
+def k7_tree(tmp_path_factory):
+    """seg_tree's files without their sidecars: every file goes through
+    the per-file K7 query."""
+    idx = str(tmp_path_factory.mktemp("k7idx"))
+    for k, nrows in enumerate(SEG_ROWS):
+        write_file(os.path.join(idx, "by_day", "2014-05-%02d.sqlite"
+                                % (k + 1)), k, nrows, sidecar=False)
+    return idx
+
+
 def ask(fd, monkeypatch, mode, **kw):
     """(points, stages, sidecar tally) of one query under a policy."""
     from dragnet_amd.query import query_load
@@ -177,18 +189,14 @@ SEG_QUERIES = {
 }
 
 
-@pytest.mark.parametrize("name", sorted(SEG_QUERIES))
-def test_segment_edges(seg_tree, gpu_engine, monkeypatch, name):
-    """Files of 0, 1, 63, 64, 65 and 257 rows: segments that end inside,
-    at and just past a wave; the same group key in several files; one
-    string at a different local code in every file."""
-    fd = datasource(seg_tree, gpu_engine)
+def check_segment_edges(fd, monkeypatch, name, served):
+    """Mode 1 against mode 0 for one SEG_QUERIES entry; `served` is the
+    tally that mode 1 must leave."""
     kw = SEG_QUERIES[name]
     want, wstages, d0 = ask(fd, monkeypatch, "0", **kw)
     got, gstages, d1 = ask(fd, monkeypatch, "1", **kw)
     assert d0["sidecar_files"] == 0
-    assert d1 == {"sidecar_files": len(SEG_ROWS), "sidecar_launches": 1,
-                  "other_files": 0}
+    assert d1 == served
     assert got == want
     assert sum(p["value"] for p in got) > 0
     assert gstages["Index List"] == wstages["Index List"]
@@ -200,6 +208,27 @@ def test_segment_edges(seg_tree, gpu_engine, monkeypatch, name):
     if name == "one_string":
         assert any(p["fields"]["host"] == "m" for p in got)
         assert gstages["Index List"]["ninputs"] > len(got)
+
+
+@pytest.mark.parametrize("name", sorted(SEG_QUERIES))
+def test_segment_edges(seg_tree, gpu_engine, monkeypatch, name):
+    """Files of 0, 1, 63, 64, 65 and 257 rows: segments that end inside,
+    at and just past a wave; the same group key in several files; one
+    string at a different local code in every file."""
+    check_segment_edges(
+        datasource(seg_tree, gpu_engine), monkeypatch, name,
+        {"sidecar_files": len(SEG_ROWS), "sidecar_launches": 1,
+         "other_files": 0})
+
+
+@pytest.mark.parametrize("name", sorted(SEG_QUERIES))
+def test_segment_edges_k7(k7_tree, gpu_engine, monkeypatch, name):
+    """The same files through the per-file K7 query: no rows (no
+    launch), one row, and rows that end inside a wave."""
+    check_segment_edges(
+        datasource(k7_tree, gpu_engine), monkeypatch, name,
+        {"sidecar_files": 0, "sidecar_launches": 0,
+         "other_files": len(SEG_ROWS)})
 
 
 def test_auto_mode_counts_rows_from_headers(seg_tree, gpu_engine,
@@ -318,3 +347,52 @@ def test_overflow_retries_with_larger_tables(seg_tree, gpu_engine,
     assert d["sidecar_files"] == len(SEG_ROWS)
     assert gpu_engine.coded_stats["retries"] - before["retries"] >= 2
     assert gpu_engine.coded_stats["launches"] - before["launches"] == 1
+
+
+def test_k7_overflow_retries_once(k7_tree, gpu_engine, monkeypatch):
+    """Two aggregation slots and three groups in every file of 63 rows
+    and more: those files overflow, and their one retry, at 16 slots,
+    holds them."""
+    from dragnet_amd.engine import colquery
+    fd = datasource(k7_tree, gpu_engine)
+    kw = dict(breakdown_specs="method")
+    want, _s, _d = ask(fd, monkeypatch, "0", **kw)
+    assert len(want) == len(METHODS) == 3
+    slots = []
+
+    class Counting(colquery._ScanContext):
+        def __init__(self, eng, cplan, agg_slots, *rest, **kwargs):
+            slots.append(agg_slots)
+            super().__init__(eng, cplan, agg_slots, *rest, **kwargs)
+
+    monkeypatch.setattr(colquery, "_ScanContext", Counting)
+    monkeypatch.setenv("DRAGNET_AGG_SLOTS", "2")
+    got, _s, d = ask(fd, monkeypatch, "1", **kw)
+    assert got == want
+    assert d["sidecar_files"] == 0 and d["other_files"] == len(SEG_ROWS)
+    # a first attempt per file; a second for the four with three groups
+    assert sorted(slots) == [2] * len(SEG_ROWS) + [16] * 4
+
+
+# ---- malformed calls are rejected before any launch ----
+
+def test_columnar_query_rejects_malformed_input(gpu_engine):
+    import torch
+    from dragnet_amd.engine import colquery
+    from dragnet_amd.query import query_load
+    dev = gpu_engine.device
+    cplan = colquery.column_plan(query_load(breakdown_specs="host"), None)
+    nf = len(cplan.field_sigs)
+    state = colquery._ScanContext(gpu_engine, cplan, 16, 16, 8 << 20,
+                                  dense=False).state
+    none = [torch.empty(0)] * nf
+    descs = gpu_engine.ops.col_descs_host([0] * nf, none, none, none).to(dev)
+    blob = torch.zeros(16, dtype=torch.uint8, device=dev)
+    values = torch.ones(4, dtype=torch.float64, device=dev)
+    short = torch.zeros(3, dtype=torch.float64, device=dev)
+    with pytest.raises(RuntimeError, match="column shorter than nrows"):
+        state.columnar_query(descs, blob, values, 4, [short])
+    with pytest.raises(RuntimeError, match="col_descs does not match"):
+        state.columnar_query(descs[:-8], blob, values, 4, [])
+    torch.cuda.synchronize(dev)
+    assert int(state.counters.sum().item()) == 0  # no row was counted
