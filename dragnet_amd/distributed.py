@@ -25,8 +25,10 @@ serialization crosses the wire:
      into a companion column) and an f64 value vector.  Payloads are
      typically <= MBs, so the latency-optimal direct all_gather beats
      ring algorithms on xGMI's 7 p2p links (SURVEY.md §5 topology
-     note); every rank re-aggregates the union (allreduce semantics),
-     vectorized via np.unique row grouping + bincount.
+     note); every rank re-aggregates the union (allreduce semantics):
+     reaggregate() groups the rows and sums their values, on the host
+     via np.unique + bincount or on the GPU with the merge_rows kernels
+     (ops/hip/merge_rows.h; DRAGNET_MERGE_GPU chooses).
   Pathological cardinality (> _PARTITION_ROWS local rows): hash-
      partition the keys with all_to_all_single so each rank owns and
      merges one key range (reduce-scatter shape), then all_gather the
@@ -146,21 +148,28 @@ def _decode_strings(blob_bytes, offs):
             for i in range(len(offs) - 1)]
 
 
-def _rebuild_table(query, codes, tagpack, vals, strings):
-    """Vectorized re-aggregation: group identical key rows with
-    np.unique, sum values with bincount, decode each UNIQUE key to the
-    Aggregator's canonical Python tuple once."""
-    merged = Aggregator(query)
-    nk = len(query.breakdowns)
-    if nk == 0:
-        total = float(vals.sum()) if vals.size else 0.0
-        if vals.size:
-            merged.table[()] = int(total) if total.is_integer() \
-                else total
-        return merged
-    X = np.concatenate([codes, tagpack[:, None]], axis=1)
+def _group_host(X, vals):
+    """Group identical rows of X [n, w] and sum vals over each group:
+    (uniq [g, w] in np.unique's order, sums f64 [g])."""
     uniq, inv = np.unique(X, axis=0, return_inverse=True)
     sums = np.bincount(inv, weights=vals, minlength=uniq.shape[0])
+    return uniq, sums
+
+
+def _scalar_table(query, vals):
+    """The table of a query without breakdowns: one scalar sum."""
+    merged = Aggregator(query)
+    if vals.size:
+        total = float(vals.sum())
+        merged.table[()] = int(total) if total.is_integer() else total
+    return merged
+
+
+def _decode_rows(query, uniq, sums, strings):
+    """Decode each UNIQUE key row [codes..., tagpack] to the
+    Aggregator's canonical Python tuple once, in row order."""
+    merged = Aggregator(query)
+    nk = len(query.breakdowns)
     for r in range(uniq.shape[0]):
         tp = int(uniq[r, nk])
         key = []
@@ -176,6 +185,168 @@ def _rebuild_table(query, codes, tagpack, vals, strings):
         v = float(sums[r])
         merged.table[tuple(key)] = int(v) if v.is_integer() else v
     return merged
+
+
+def _rebuild_table(query, codes, tagpack, vals, strings):
+    """Vectorized host re-aggregation of one dense table: group
+    identical key rows with np.unique and sum values with bincount
+    (_group_host), then decode the unique rows (_decode_rows).  The
+    per-row Python of _encode_table and of the decode loop is what it
+    was; vectorising either is a separate piece of work."""
+    if len(query.breakdowns) == 0:
+        return _scalar_table(query, vals)
+    X = np.concatenate([codes, tagpack[:, None]], axis=1)
+    return _decode_rows(query, *_group_host(X, vals), strings)
+
+
+# ---- re-aggregation of gathered tables ---------------------------------
+
+MERGE_GPU_ROWS_DEFAULT = float("inf")
+
+
+def _env_merge_gpu_rows():
+    """Total rows from which DRAGNET_MERGE_GPU=auto groups on the GPU
+    (DRAGNET_MERGE_GPU_ROWS).  Measured in profiles/r08_merge_rows.md:
+    the device path wins by far at low and medium cardinality but not
+    when every row is distinct and 8 columns wide, so no measured size
+    wins at every cardinality and the default is infinity: auto mode
+    never selects it, DRAGNET_MERGE_GPU=1 does."""
+    v = os.environ.get("DRAGNET_MERGE_GPU_ROWS")
+    if v is None:
+        return MERGE_GPU_ROWS_DEFAULT
+    try:
+        return int(v)
+    except ValueError:
+        return float("inf")
+
+
+def _merge_on_gpu(n_rows, nk):
+    """Path choice of the row grouping (DRAGNET_MERGE_GPU): "0" always
+    the host; "1" the GPU whenever one is visible; "auto" the GPU from
+    DRAGNET_MERGE_GPU_ROWS rows up.  A table without breakdowns is a
+    scalar sum and an empty one is nothing: both stay on the host."""
+    mode = os.environ.get("DRAGNET_MERGE_GPU", "auto")
+    if mode == "0" or nk < 1 or n_rows == 0:
+        return False
+    if mode != "1" and n_rows < _env_merge_gpu_rows():
+        return False
+    import torch
+    return torch.cuda.is_available()
+
+
+def _np(a):
+    return a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+
+
+def _group_rows_host(parts, remaps, nk):
+    """Remap (numpy fancy indexing), concatenate, group: the reference
+    the device path must equal bit for bit."""
+    all_rows, all_vals = [], []
+    for r, (codes, tags, vals) in enumerate(parts):
+        rt = _np(tags).astype(np.int64, copy=False)
+        rc = _np(codes).reshape(rt.shape[0], nk).astype(np.int64,
+                                                        copy=True)
+        if remaps is not None:
+            for j in range(nk):
+                is_str = ((rt >> (2 * j)) & 3) == _EL_STR
+                if is_str.any():
+                    rc[is_str, j] = remaps[r][rc[is_str, j]]
+        all_rows.append(np.concatenate([rc, rt[:, None]], axis=1))
+        all_vals.append(_np(vals).astype(np.float64, copy=False))
+    return _group_host(np.concatenate(all_rows), np.concatenate(all_vals))
+
+
+def _group_rows_device(parts, remaps, nk, device):
+    """One merge_rows call over the parts as segments; the remap runs
+    inside the kernel.  Parts already on the GPU are never copied to
+    the host; only the distinct rows and their sums come back, sorted
+    into np.unique's order (lexicographic over the columns left to
+    right, as signed int64).  None when the kernel reports sums that
+    depend on the order of its adds."""
+    import torch
+
+    from .ops import load_ops
+    ops = load_ops(required=True)  # a missing extension is an error
+    if device is None or torch.device(device).type != "cuda":
+        on_gpu = [p[0].device for p in parts
+                  if torch.is_tensor(p[0]) and p[0].is_cuda]
+        device = on_gpu[0] if on_gpu else torch.device(
+            "cuda", torch.cuda.current_device())
+
+    def up(a, dtype):
+        return torch.as_tensor(a).to(device=device, dtype=dtype)
+
+    rows = torch.cat([
+        torch.cat([up(codes, torch.int64).reshape(-1, nk),
+                   up(tags, torch.int64).reshape(-1, 1)], dim=1)
+        for codes, tags, _vals in parts])
+    vals = torch.cat([up(v, torch.float64) for _c, _t, v in parts])
+    kw = {}
+    if remaps is not None:
+        def offsets(sizes):
+            return torch.from_numpy(
+                np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64))
+        kw = dict(
+            seg_start=offsets([int(_t.shape[0]) for _c, _t, _v in parts]),
+            remap=up(np.concatenate(remaps), torch.int64),
+            remap_off=offsets([len(m) for m in remaps]))
+    uniq, sums, exact = ops.merge_rows(rows, vals, nk, **kw)
+    if not exact:
+        return None
+    uniq = uniq.cpu().numpy()
+    sums = sums.cpu().numpy()
+    order = np.lexsort(uniq.T[::-1])  # last key is the primary one
+    return uniq[order], sums[order]
+
+
+def _group_rows(parts, remaps, nk, device=None):
+    """Group the rows [codes..., tagpack] of all parts and sum their
+    values: (uniq [g, nk + 1], sums [g]) in np.unique's order.  remaps
+    is one int64 table per part for its string-tagged codes, or None.
+
+    The result is bit-identical whichever path runs.  Device f64 adds
+    come in no fixed order, and only sums of non-negative integers that
+    stay below 2^53 are independent of the order, so the kernel reports
+    anything else (a fractional, negative, NaN or infinite weight, a
+    value or a sum at or beyond 2^53) and the host path then answers."""
+    n_rows = sum(int(p[1].shape[0]) for p in parts)
+    out = None
+    if _merge_on_gpu(n_rows, nk):
+        out = _group_rows_device(parts, remaps, nk, device)
+    if out is None:
+        out = _group_rows_host(parts, remaps, nk)
+    return out
+
+
+def reaggregate(query, parts, strings_per_part, device=None):
+    """The step after the gather; needs no process group.  parts is
+    one (codes [n_r, nk], tagpack [n_r], vals [n_r]) per rank, numpy or
+    torch on any device, with string codes in that rank's dictionary
+    strings_per_part[r].  Builds the global dictionary (first seen
+    first, in rank order) and the per-rank remap tables on the host,
+    since strings are few; remaps, groups and sums the rows
+    (_group_rows: host or GPU, same result), and decodes the distinct
+    rows into the merged Aggregator, in np.unique's row order."""
+    nk = len(query.breakdowns)
+    if nk == 0:
+        vals = [_np(v).astype(np.float64, copy=False)
+                for _c, _t, v in parts]
+        return _scalar_table(
+            query, np.concatenate(vals) if vals else np.zeros(0))
+    gdict = {}
+    gstrings = []
+    remaps = []
+    for rstr in strings_per_part:
+        remap = np.empty(len(rstr), dtype=np.int64)
+        for i, s in enumerate(rstr):
+            gi = gdict.get(s)
+            if gi is None:
+                gi = gdict[s] = len(gstrings)
+                gstrings.append(s)
+            remap[i] = gi
+        remaps.append(remap)
+    uniq, sums = _group_rows(parts, remaps, nk, device)
+    return _decode_rows(query, uniq, sums, gstrings)
 
 
 # ---- collectives -------------------------------------------------------
@@ -245,39 +416,17 @@ def merge_tables_tensor(agg, query, device=None, group=None):
         dev(np.frombuffer(blob, dtype=np.uint8).copy(), torch.uint8),
         list(ns_blob), device, group)
 
-    # C2: global dictionary + per-rank remap, then concatenate
-    gdict = {}
-    gstrings = []
-    all_codes = []
-    all_tags = []
-    all_vals = []
+    # C2 + C1: only the string blobs are decoded here; the gathered
+    # code, tag and value tensors go to reaggregate as they are
+    strings_per_part = []
+    parts = []
     for r in range(world):
         sb = bytes(g_blob[r].cpu().numpy().tobytes())
-        so = g_soffs[r].cpu().numpy()
-        rstr = _decode_strings(sb, so)
-        remap = np.empty(max(len(rstr), 1), dtype=np.int64)
-        for i, s in enumerate(rstr):
-            gi = gdict.get(s)
-            if gi is None:
-                gi = gdict[s] = len(gstrings)
-                gstrings.append(s)
-            remap[i] = gi
-        rc = g_codes[r].cpu().numpy().reshape(-1, nk).copy() \
-            if nk else np.zeros((int(ns_rows[r]), 0), dtype=np.int64)
-        rt = g_tags[r].cpu().numpy()
-        for j in range(nk):
-            is_str = ((rt >> (2 * j)) & 3) == _EL_STR
-            if is_str.any():
-                rc[is_str, j] = remap[rc[is_str, j]]
-        all_codes.append(rc)
-        all_tags.append(rt)
-        all_vals.append(g_vals[r].cpu().numpy())
-
-    merged = _rebuild_table(
-        query,
-        np.concatenate(all_codes) if all_codes else
-        np.zeros((0, nk), np.int64),
-        np.concatenate(all_tags), np.concatenate(all_vals), gstrings)
+        strings_per_part.append(
+            _decode_strings(sb, g_soffs[r].cpu().numpy()))
+        parts.append((g_codes[r].reshape(int(ns_rows[r]), nk),
+                      g_tags[r], g_vals[r]))
+    merged = reaggregate(query, parts, strings_per_part, device=device)
     merged.ninputs = agg.ninputs  # per-rank; callers sum via counters
     merged.ndropped_nonnumeric = agg.ndropped_nonnumeric
     return merged
@@ -361,15 +510,16 @@ def _merge_partitioned(query, codes, tagpack, vals, strings, device,
     dist.all_to_all_single(
         recv, send, list(out_counts.cpu().numpy()),
         list(in_counts.cpu().numpy()), group=group)
-    mine = recv.cpu().numpy().reshape(-1, nk + 2)
 
-    # merge my partition, then share the merged partitions
-    my_codes = mine[:, :nk]
-    my_tags = mine[:, nk]
-    my_vals = mine[:, nk + 1].view(np.float64)
-    X = np.concatenate([my_codes, my_tags[:, None]], axis=1)
-    uniq, inv = np.unique(X, axis=0, return_inverse=True)
-    sums = np.bincount(inv, weights=my_vals, minlength=uniq.shape[0])
+    def split(flat):
+        """[n * (nk + 2)] i64 wire rows -> (codes, tagpack, vals)."""
+        m = flat.reshape(-1, nk + 2)
+        return (m[:, :nk], m[:, nk],
+                m[:, nk + 1].contiguous().view(torch.float64))
+
+    # merge my partition (codes are global already: no segments, no
+    # remap), then share the merged partitions
+    uniq, sums = _group_rows([split(recv)], None, nk, device)
     out = np.concatenate([uniq, sums.view(np.int64)[:, None]], axis=1)
 
     sz = torch.tensor([out.shape[0] * (nk + 2)], dtype=torch.int64,
@@ -380,11 +530,10 @@ def _merge_partitioned(query, codes, tagpack, vals, strings, device,
     szs = [int(s.item()) for s in szs]
     parts = _all_gather_padded(dev(out.reshape(-1), torch.int64), szs,
                                device, group)
-    allrows = np.concatenate(
-        [p.cpu().numpy().reshape(-1, nk + 2) for p in parts])
-    merged = _rebuild_table(
-        query, allrows[:, :nk], allrows[:, nk],
-        allrows[:, nk + 1].view(np.float64), gstrings)
+    # every partition is in global codes: each rank's "dictionary" is
+    # the global one and its remap the identity
+    merged = reaggregate(query, [split(p) for p in parts],
+                         [gstrings] * world, device=device)
     merged.ninputs = agg.ninputs
     merged.ndropped_nonnumeric = agg.ndropped_nonnumeric
     return merged

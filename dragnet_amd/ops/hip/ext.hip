@@ -160,6 +160,141 @@ void xpose_build(torch::Tensor data, torch::Tensor sstart,
          (uint32_t)n_slots, (int)gran_log, (uint8_t*)xb.data_ptr());
 }
 
+// Group identical rows and sum their values (merge_rows.h): rows is
+// int64 [n, nk + 1] (key codes, then the tag pack), vals f64 [n].  With
+// seg_start / remap / remap_off the rows come in segments, each with a
+// remap table for its string-tagged codes (remap concatenated, the
+// tables delimited by remap_off); the three go together.  Returns the g
+// distinct rows (any order), their sums, and whether the sums are exact:
+// if not they depend on the order of the device's adds, and the caller
+// must not use them.  hash_mask narrows the home slots (tests);
+// max_blocks > 0 caps the grid.  Syncs once, to learn g.
+std::tuple<torch::Tensor, torch::Tensor, bool> merge_rows(
+    torch::Tensor rows, torch::Tensor vals, int64_t nk,
+    c10::optional<torch::Tensor> seg_start,
+    c10::optional<torch::Tensor> remap,
+    c10::optional<torch::Tensor> remap_off, int64_t hash_mask,
+    int64_t max_blocks) {
+  CHECK_GPU(rows);
+  CHECK_GPU(vals);
+  TORCH_CHECK(nk >= 1 && nk <= MAX_KEY, "merge_rows: nk must be 1..",
+              (int)MAX_KEY);
+  const int64_t w = nk + 1;
+  TORCH_CHECK(rows.scalar_type() == torch::kInt64 && rows.dim() == 2 &&
+                  rows.size(1) == w && rows.is_contiguous(),
+              "merge_rows: rows must be contiguous int64 [n, nk + 1]");
+  const int64_t n = rows.size(0);
+  TORCH_CHECK(vals.scalar_type() == torch::kFloat64 && vals.dim() == 1 &&
+                  vals.size(0) == n && vals.is_contiguous() &&
+                  vals.device() == rows.device(),
+              "merge_rows: vals must be contiguous float64 [n] on the "
+              "device of rows");
+  TORCH_CHECK(n < ((int64_t)1 << 31), "merge_rows: n exceeds 2^31 rows");
+  TORCH_CHECK(max_blocks >= 0, "merge_rows: max_blocks is negative");
+  const bool segmented = seg_start.has_value();
+  TORCH_CHECK(segmented == remap.has_value() &&
+                  segmented == remap_off.has_value(),
+              "merge_rows: seg_start, remap and remap_off go together");
+
+  const auto dev = rows.device();
+  auto on_dev = [&](torch::ScalarType t) {
+    return torch::dtype(t).device(dev);
+  };
+  MergeArgs A = {};
+  torch::Tensor seg_dev, off_dev, remap_dev;
+  if (segmented) {
+    // the segment structure is a few entries per rank: validated on the
+    // host, since the kernel indexes remap through it
+    auto seg = seg_start->to(torch::kCPU, torch::kInt64).contiguous();
+    auto off = remap_off->to(torch::kCPU, torch::kInt64).contiguous();
+    TORCH_CHECK(seg.dim() == 1 && seg.numel() >= 2 &&
+                    off.dim() == 1 && off.numel() == seg.numel(),
+                "merge_rows: seg_start and remap_off need nseg + 1 "
+                "entries each");
+    TORCH_CHECK(remap->scalar_type() == torch::kInt64 &&
+                    remap->dim() == 1 && remap->is_contiguous() &&
+                    remap->device() == dev,
+                "merge_rows: remap must be contiguous int64 on the "
+                "device of rows");
+    const int64_t* sp = seg.data_ptr<int64_t>();
+    const int64_t* op = off.data_ptr<int64_t>();
+    const int64_t nseg = seg.numel() - 1;
+    TORCH_CHECK(sp[0] == 0 && op[0] == 0,
+                "merge_rows: seg_start and remap_off start at 0");
+    for (int64_t i = 0; i < nseg; i++)
+      TORCH_CHECK(sp[i] <= sp[i + 1] && op[i] <= op[i + 1],
+                  "merge_rows: seg_start and remap_off must not decrease");
+    TORCH_CHECK(sp[nseg] == n, "merge_rows: seg_start ends at ", sp[nseg],
+                ", rows has ", n);
+    TORCH_CHECK(op[nseg] == remap->numel(), "merge_rows: remap_off ends at ",
+                op[nseg], ", remap has ", remap->numel());
+    seg_dev = seg.to(torch::kInt32).to(dev);
+    off_dev = off.to(dev);
+    remap_dev = *remap;
+    A.nseg = (uint32_t)nseg;
+    A.seg_start = (const uint32_t*)seg_dev.data_ptr();
+    A.remap = (const long long*)remap_dev.data_ptr();
+    A.remap_off = (const long long*)off_dev.data_ptr();
+  }
+  if (n == 0)
+    return std::make_tuple(torch::empty({0, w}, on_dev(torch::kInt64)),
+                           torch::empty({0}, on_dev(torch::kFloat64)), true);
+
+  c10::DeviceGuard guard(dev);
+  // a tile is loaded 16 bytes at a time from the base of rows
+  if ((uintptr_t)rows.data_ptr() % 16 != 0) rows = rows.clone();
+
+  // next power of two at or above 2n, floor 1024; n < 2^31 rows still
+  // fit a table of 2^31 slots, the most a uint32 slot index addresses
+  int64_t slots = 1024;
+  while (slots < 2 * n && slots < ((int64_t)1 << 31)) slots *= 2;
+  torch::Tensor state, keys, sum, out_rows, out_sums, meta;
+  try {
+    state = torch::zeros({slots}, on_dev(torch::kInt32));
+    keys = torch::zeros({slots * w}, on_dev(torch::kInt64));
+    sum = torch::zeros({slots}, on_dev(torch::kFloat64));
+    out_rows = torch::empty({n, w}, on_dev(torch::kInt64));
+    out_sums = torch::empty({n}, on_dev(torch::kFloat64));
+    meta = torch::zeros({2}, on_dev(torch::kInt32));  // g, status
+  } catch (const c10::OutOfMemoryError& e) {
+    std::string why = e.what_without_backtrace();
+    TORCH_CHECK(false, "cannot allocate the merge table (", slots,
+                " slots for ", n, " rows): device allocation failed (",
+                why.substr(0, why.find('\n')), ")");
+  }
+  uint32_t* meta_p = (uint32_t*)meta.data_ptr();
+  A.rows = (const long long*)rows.data_ptr();
+  A.vals = (const double*)vals.data_ptr();
+  A.n = (uint32_t)n;
+  A.hash_mask = (uint64_t)hash_mask;
+  A.T.state = (uint32_t*)state.data_ptr();
+  A.T.keys = (long long*)keys.data_ptr();
+  A.T.sum = (double*)sum.data_ptr();
+  A.T.slots = (uint32_t)slots;
+  A.T.w = (int)w;
+  A.status = meta_p + 1;
+
+  int64_t blocks = std::min<int64_t>((n + MERGE_TILE - 1) / MERGE_TILE,
+                                     GRID_CAP);
+  if (max_blocks > 0) blocks = std::min(blocks, max_blocks);
+  launch("merge_insert", merge_insert_kernel, dim3((uint32_t)blocks),
+         dim3(MERGE_TILE), 0, A);
+  launch("merge_compact", merge_compact_kernel,
+         dim3((uint32_t)((slots + 255) / 256)), dim3(256), 0, A.T,
+         (long long*)out_rows.data_ptr(), (double*)out_sums.data_ptr(),
+         meta_p, meta_p + 1);
+  auto host = meta.cpu();  // waits for both kernels
+  const int64_t g = host.data_ptr<int32_t>()[0];
+  const uint32_t status = (uint32_t)host.data_ptr<int32_t>()[1];
+  TORCH_CHECK(!(status & MERGE_BAD_CODE),
+              "merge_rows: a string-tagged code lies outside its segment's "
+              "remap table (seg_start / remap_off do not describe these "
+              "rows)");
+  TORCH_CHECK(!(status & MERGE_FULL), "merge_rows: merge table full");
+  return std::make_tuple(out_rows.narrow(0, 0, g), out_sums.narrow(0, 0, g),
+                         !(status & MERGE_INEXACT));
+}
+
 // The bound state of one scan context.  Built once from keyword
 // arguments; allocates and owns every tensor its PlanView / AggTable /
 // StrDict / NumDict descriptors point at, so their lifetime does not
@@ -700,6 +835,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("newline_index", &dn::newline_index, "device-side newline index");
   m.def("xpose_build", &dn::xpose_build, "device-side wave transpose");
   m.def("col_descs_host", &dn::col_descs_host);
+  m.def("merge_rows", &dn::merge_rows, py::arg("rows"), py::arg("vals"),
+        py::arg("nk"), py::arg("seg_start") = py::none(),
+        py::arg("remap") = py::none(), py::arg("remap_off") = py::none(),
+        py::arg("hash_mask") = -1, py::arg("max_blocks") = 0,
+        "group identical int64 rows, sum their f64 values -> "
+        "(uniq [g, nk + 1], sums [g], exact)");
   m.def("lds_bytes", &dn::lds_bytes, py::arg("nf"), py::arg("nm"),
         py::arg("ns") = 0, py::arg("columnar") = false,
         "dynamic LDS bytes of a scan / columnar launch (host only)");

@@ -18,7 +18,8 @@
 // Layers (docs/DESIGN.md): scan_text.h, scan_record.h (record semantics,
 // host-compilable too), scan_tables.h (device only), the kernels here,
 // scan_rehash.h (device only: table growth between launches),
-// scan_columns.h (device only: the index queries over typed columns).
+// scan_columns.h (device only: the index queries over typed columns),
+// merge_rows.h (device only: re-aggregation of merged multi-GPU tables).
 
 #include "common.h"
 #include <hip/hip_runtime.h>
@@ -593,5 +594,8 @@ __global__ void extract_numdict_kernel(NumDict D, double* out_vals,
 // index queries over typed columns (K7 and the columnar sidecars);
 // after everything else, for the same reason
 #include "scan_columns.h"
+
+// group-by-sum of the merged multi-GPU tables; last again
+#include "merge_rows.h"
 
 }  // extern "C++"
