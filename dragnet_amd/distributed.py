@@ -206,11 +206,11 @@ MERGE_GPU_ROWS_DEFAULT = float("inf")
 
 def _env_merge_gpu_rows():
     """Total rows from which DRAGNET_MERGE_GPU=auto groups on the GPU
-    (DRAGNET_MERGE_GPU_ROWS).  Measured in profiles/r08_merge_rows.md:
-    the device path wins by far at low and medium cardinality but not
-    when every row is distinct and 8 columns wide, so no measured size
-    wins at every cardinality and the default is infinity: auto mode
-    never selects it, DRAGNET_MERGE_GPU=1 does."""
+    (DRAGNET_MERGE_GPU_ROWS).  profiles/r08_merge_rows.md measured no
+    size that wins at every cardinality, hence the default of infinity:
+    auto mode never selects it, DRAGNET_MERGE_GPU=1 does.  With the
+    rows ordered on the device (profiles/r09_sort_rows.md) the same
+    rule gives 10000; the default is unchanged so far."""
     v = os.environ.get("DRAGNET_MERGE_GPU_ROWS")
     if v is None:
         return MERGE_GPU_ROWS_DEFAULT
@@ -259,9 +259,10 @@ def _group_rows_host(parts, remaps, nk):
 def _group_rows_device(parts, remaps, nk, device):
     """One merge_rows call over the parts as segments; the remap runs
     inside the kernel.  Parts already on the GPU are never copied to
-    the host; only the distinct rows and their sums come back, sorted
-    into np.unique's order (lexicographic over the columns left to
-    right, as signed int64).  None when the kernel reports sums that
+    the host; only the distinct rows and their sums come back, already
+    in np.unique's order (lexicographic over the columns left to right,
+    as signed int64: the radix sort of ops/hip/sort_rows.h, behind
+    merge_rows' sort=True).  None when the kernel reports sums that
     depend on the order of its adds."""
     import torch
 
@@ -290,13 +291,10 @@ def _group_rows_device(parts, remaps, nk, device):
             seg_start=offsets([int(_t.shape[0]) for _c, _t, _v in parts]),
             remap=up(np.concatenate(remaps), torch.int64),
             remap_off=offsets([len(m) for m in remaps]))
-    uniq, sums, exact = ops.merge_rows(rows, vals, nk, **kw)
+    uniq, sums, exact = ops.merge_rows(rows, vals, nk, sort=True, **kw)
     if not exact:
         return None
-    uniq = uniq.cpu().numpy()
-    sums = sums.cpu().numpy()
-    order = np.lexsort(uniq.T[::-1])  # last key is the primary one
-    return uniq[order], sums[order]
+    return uniq.cpu().numpy(), sums.cpu().numpy()
 
 
 def _group_rows(parts, remaps, nk, device=None):

@@ -160,6 +160,131 @@ void xpose_build(torch::Tensor data, torch::Tensor sstart,
          (uint32_t)n_slots, (int)gran_log, (uint8_t*)xb.data_ptr());
 }
 
+namespace {
+
+uint32_t sort_span_grid(int64_t n) {
+  return (uint32_t)std::min<int64_t>((n + SORT_BLOCK - 1) / SORT_BLOCK,
+                                     GRID_CAP);
+}
+
+// The passes of the row sort (sort_rows.h) on the current stream: the
+// stable permutation that orders rows [n, w], n >= 2, as int32 [n].
+// span_dev is what sort_span_kernel left (AND words, then OR words);
+// span_host is the same on the host and is needed only for n >
+// SORT_TILE, where the host lists the passes.  Never syncs.
+torch::Tensor sort_passes(const long long* rows, int64_t n, int w,
+                          const unsigned long long* span_dev,
+                          const unsigned long long* span_host,
+                          torch::Device dev) {
+  auto on_dev = [&](torch::ScalarType t) {
+    return torch::dtype(t).device(dev);
+  };
+  struct Column { int c; int nshift; int shift[8]; };
+  Column cols[MERGE_W];
+  int ncols = 0;
+  if (n > SORT_TILE) {
+    for (int c = w - 1; c >= 0; c--) {
+      const unsigned long long diff = span_host[w + c] ^ span_host[c];
+      Column col = {c, 0, {}};
+      for (int b = 0; b < 8; b++)
+        if ((diff >> (8 * b)) & 0xffull) col.shift[col.nshift++] = 8 * b;
+      if (col.nshift) cols[ncols++] = col;
+    }
+    if (ncols == 0) return torch::arange(n, on_dev(torch::kInt32));
+  }
+  const int64_t ntiles = (n + SORT_TILE - 1) / SORT_TILE;
+  const int64_t total = ntiles * SORT_BINS;
+  const int64_t nsums = (total + SORT_SCAN_TILE - 1) / SORT_SCAN_TILE;
+  torch::Tensor key[2], idx[2], hist, sums;
+  try {
+    idx[0] = torch::empty({n}, on_dev(torch::kInt32));
+    if (n > SORT_TILE) {
+      idx[1] = torch::empty({n}, on_dev(torch::kInt32));
+      key[0] = torch::empty({n}, on_dev(torch::kInt64));
+      key[1] = torch::empty({n}, on_dev(torch::kInt64));
+      hist = torch::empty({total}, on_dev(torch::kInt32));
+      sums = torch::empty({nsums}, on_dev(torch::kInt32));
+    }
+  } catch (const c10::OutOfMemoryError& e) {
+    std::string why = e.what_without_backtrace();
+    TORCH_CHECK(false, "cannot allocate the sort buffers (two key and two "
+                "index arrays and the histograms for ", n,
+                " rows): device allocation failed (",
+                why.substr(0, why.find('\n')), ")");
+  }
+  if (n <= SORT_TILE) {
+    launch("sort_small", sort_small_kernel, dim3(1), dim3(SORT_BLOCK), 0,
+           rows, (uint32_t)n, w, span_dev, (uint32_t*)idx[0].data_ptr());
+    return idx[0];
+  }
+  sort_key_t* kp[2] = {(sort_key_t*)key[0].data_ptr(),
+                       (sort_key_t*)key[1].data_ptr()};
+  uint32_t* ip[2] = {(uint32_t*)idx[0].data_ptr(),
+                     (uint32_t*)idx[1].data_ptr()};
+  uint32_t* hp = (uint32_t*)hist.data_ptr();
+  uint32_t* sp = (uint32_t*)sums.data_ptr();
+  int cur = 0;
+  for (int i = 0; i < ncols; i++) {
+    launch("sort_key", sort_key_kernel,
+           dim3((uint32_t)((n + SORT_BLOCK - 1) / SORT_BLOCK)),
+           dim3(SORT_BLOCK), 0, rows, (uint32_t)n, w, cols[i].c,
+           i == 0 ? (const uint32_t*)nullptr : (const uint32_t*)ip[cur],
+           kp[cur], ip[cur]);
+    for (int j = 0; j < cols[i].nshift; j++) {
+      const int shift = cols[i].shift[j];
+      launch("sort_hist", sort_hist_kernel, dim3((uint32_t)ntiles),
+             dim3(SORT_BLOCK), 0, (const sort_key_t*)kp[cur], (uint32_t)n,
+             shift, hp, (uint32_t)ntiles);
+      launch("sort_scan", sort_scan_kernel, dim3((uint32_t)nsums),
+             dim3(SORT_BLOCK), 0, hp, (uint32_t)total, sp);
+      launch("sort_scan_sums", sort_scan_sums_kernel, dim3(1),
+             dim3(SORT_BLOCK), 0, sp, (uint32_t)nsums);
+      launch("sort_scatter", sort_scatter_kernel, dim3((uint32_t)ntiles),
+             dim3(SORT_BLOCK), 0, (const sort_key_t*)kp[cur],
+             (const uint32_t*)ip[cur], kp[cur ^ 1], ip[cur ^ 1],
+             (uint32_t)n, shift, (const uint32_t*)hp, (const uint32_t*)sp,
+             (uint32_t)ntiles);
+      cur ^= 1;
+    }
+  }
+  return idx[cur];
+}
+
+}  // namespace
+
+// The stable permutation that sorts the rows of a contiguous int64
+// [n, w] GPU tensor lexicographically, column 0 first, each word as a
+// signed int64: np.lexsort(rows.T[::-1]), as int32 [n] (sort_rows.h).
+// n < 2 launches nothing; n <= SORT_TILE never syncs; beyond that it
+// syncs once, to read which bytes vary, and returns the identity with no
+// pass when none does.
+torch::Tensor sort_rows(torch::Tensor rows) {
+  CHECK_GPU(rows);
+  TORCH_CHECK(rows.scalar_type() == torch::kInt64 && rows.dim() == 2 &&
+                  rows.is_contiguous() && rows.size(1) >= 1 &&
+                  rows.size(1) <= MERGE_W,
+              "sort_rows: rows must be contiguous int64 [n, w] with w in "
+              "1..", (int)MERGE_W);
+  const int64_t n = rows.size(0);
+  const int w = (int)rows.size(1);
+  TORCH_CHECK(n < ((int64_t)1 << 31), "sort_rows: n exceeds 2^31 rows");
+  const auto dev = rows.device();
+  if (n < 2) return torch::zeros({n}, torch::dtype(torch::kInt32).device(dev));
+
+  c10::DeviceGuard guard(dev);
+  auto span = torch::zeros({2 * w}, torch::dtype(torch::kInt64).device(dev));
+  span.narrow(0, 0, w).fill_(-1);
+  const long long* rp = (const long long*)rows.data_ptr();
+  unsigned long long* span_p = (unsigned long long*)span.data_ptr();
+  launch("sort_span", sort_span_kernel, dim3(sort_span_grid(n)),
+         dim3(SORT_BLOCK), 0, rp, (uint32_t)n, (const uint32_t*)nullptr, w,
+         span_p);
+  if (n <= SORT_TILE) return sort_passes(rp, n, w, span_p, nullptr, dev);
+  auto host = span.cpu();  // waits for the span
+  return sort_passes(rp, n, w, span_p,
+                     (const unsigned long long*)host.data_ptr(), dev);
+}
+
 // Group identical rows and sum their values (merge_rows.h): rows is
 // int64 [n, nk + 1] (key codes, then the tag pack), vals f64 [n].  With
 // seg_start / remap / remap_off the rows come in segments, each with a
@@ -168,13 +293,17 @@ void xpose_build(torch::Tensor data, torch::Tensor sstart,
 // distinct rows (any order), their sums, and whether the sums are exact:
 // if not they depend on the order of the device's adds, and the caller
 // must not use them.  hash_mask narrows the home slots (tests);
-// max_blocks > 0 caps the grid.  Syncs once, to learn g.
+// max_blocks > 0 caps the grid.  With sort the rows and sums come back
+// in np.unique's order (sort_rows.h): the span kernel runs behind the
+// compaction on the device-side count, its words come back in the copy
+// that fetches g, and the sort passes are enqueued after it.  Syncs
+// once either way, to learn g.
 std::tuple<torch::Tensor, torch::Tensor, bool> merge_rows(
     torch::Tensor rows, torch::Tensor vals, int64_t nk,
     c10::optional<torch::Tensor> seg_start,
     c10::optional<torch::Tensor> remap,
     c10::optional<torch::Tensor> remap_off, int64_t hash_mask,
-    int64_t max_blocks) {
+    int64_t max_blocks, bool sort) {
   CHECK_GPU(rows);
   CHECK_GPU(vals);
   TORCH_CHECK(nk >= 1 && nk <= MAX_KEY, "merge_rows: nk must be 1..",
@@ -255,7 +384,9 @@ std::tuple<torch::Tensor, torch::Tensor, bool> merge_rows(
     sum = torch::zeros({slots}, on_dev(torch::kFloat64));
     out_rows = torch::empty({n, w}, on_dev(torch::kInt64));
     out_sums = torch::empty({n}, on_dev(torch::kFloat64));
-    meta = torch::zeros({2}, on_dev(torch::kInt32));  // g, status
+    // g, status; with sort the span behind them: AND words, OR words
+    meta = torch::zeros({2 + (sort ? 4 * w : 0)}, on_dev(torch::kInt32));
+    if (sort) meta.narrow(0, 2, 2 * w).fill_(-1);
   } catch (const c10::OutOfMemoryError& e) {
     std::string why = e.what_without_backtrace();
     TORCH_CHECK(false, "cannot allocate the merge table (", slots,
@@ -283,7 +414,12 @@ std::tuple<torch::Tensor, torch::Tensor, bool> merge_rows(
          dim3((uint32_t)((slots + 255) / 256)), dim3(256), 0, A.T,
          (long long*)out_rows.data_ptr(), (double*)out_sums.data_ptr(),
          meta_p, meta_p + 1);
-  auto host = meta.cpu();  // waits for both kernels
+  unsigned long long* span_p = (unsigned long long*)(meta_p + 2);
+  if (sort)  // sized for n; reads g on the device and exits beyond it
+    launch("sort_span", sort_span_kernel, dim3(sort_span_grid(n)),
+           dim3(SORT_BLOCK), 0, (const long long*)out_rows.data_ptr(),
+           (uint32_t)n, (const uint32_t*)meta_p, (int)w, span_p);
+  auto host = meta.cpu();  // waits for the kernels
   const int64_t g = host.data_ptr<int32_t>()[0];
   const uint32_t status = (uint32_t)host.data_ptr<int32_t>()[1];
   TORCH_CHECK(!(status & MERGE_BAD_CODE),
@@ -291,6 +427,22 @@ std::tuple<torch::Tensor, torch::Tensor, bool> merge_rows(
               "remap table (seg_start / remap_off do not describe these "
               "rows)");
   TORCH_CHECK(!(status & MERGE_FULL), "merge_rows: merge table full");
+  if (sort && g > 1) {
+    auto perm = sort_passes(
+        (const long long*)out_rows.data_ptr(), g, (int)w, span_p,
+        (const unsigned long long*)(host.data_ptr<int32_t>() + 2), dev);
+    auto sorted_rows = torch::empty({g, w}, on_dev(torch::kInt64));
+    auto sorted_sums = torch::empty({g}, on_dev(torch::kFloat64));
+    launch("sort_gather", sort_gather_kernel,
+           dim3((uint32_t)((g + MERGE_TILE - 1) / MERGE_TILE)),
+           dim3(MERGE_TILE), 0, (const long long*)out_rows.data_ptr(),
+           (const double*)out_sums.data_ptr(),
+           (const uint32_t*)perm.data_ptr(), (uint32_t)g, (int)w,
+           (long long*)sorted_rows.data_ptr(),
+           (double*)sorted_sums.data_ptr());
+    return std::make_tuple(sorted_rows, sorted_sums,
+                           !(status & MERGE_INEXACT));
+  }
   return std::make_tuple(out_rows.narrow(0, 0, g), out_sums.narrow(0, 0, g),
                          !(status & MERGE_INEXACT));
 }
@@ -839,8 +991,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("nk"), py::arg("seg_start") = py::none(),
         py::arg("remap") = py::none(), py::arg("remap_off") = py::none(),
         py::arg("hash_mask") = -1, py::arg("max_blocks") = 0,
+        py::arg("sort") = false,
         "group identical int64 rows, sum their f64 values -> "
-        "(uniq [g, nk + 1], sums [g], exact)");
+        "(uniq [g, nk + 1], sums [g], exact); sort: in np.unique's order");
+  m.def("sort_rows", &dn::sort_rows, py::arg("rows"),
+        "stable lexicographic sorting permutation (int32 [n]) of int64 "
+        "rows [n, w] on the GPU");
   m.def("lds_bytes", &dn::lds_bytes, py::arg("nf"), py::arg("nm"),
         py::arg("ns") = 0, py::arg("columnar") = false,
         "dynamic LDS bytes of a scan / columnar launch (host only)");
@@ -877,5 +1033,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("grow_sdata", &dn::ScanState::grow_sdata, py::arg("new_bytes"))
       .def("grow_ndict", &dn::ScanState::grow_ndict, py::arg("new_slots"));
   m.attr("MAX_KEY") = (int)dn::MAX_KEY;
+  m.attr("SORT_TILE") = (int)dn::SORT_TILE;
   m.attr("MAX_FIELDS") = (int)dn::MAX_FIELDS;
 }

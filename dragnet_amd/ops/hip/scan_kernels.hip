@@ -19,7 +19,8 @@
 // host-compilable too), scan_tables.h (device only), the kernels here,
 // scan_rehash.h (device only: table growth between launches),
 // scan_columns.h (device only: the index queries over typed columns),
-// merge_rows.h (device only: re-aggregation of merged multi-GPU tables).
+// merge_rows.h (device only: re-aggregation of merged multi-GPU tables),
+// sort_rows.h (device only: radix sort of the merged rows).
 
 #include "common.h"
 #include <hip/hip_runtime.h>
@@ -597,5 +598,8 @@ __global__ void extract_numdict_kernel(NumDict D, double* out_vals,
 
 // group-by-sum of the merged multi-GPU tables; last again
 #include "merge_rows.h"
+
+// radix sort of the merged rows into np.unique's order; last again
+#include "sort_rows.h"
 
 }  // extern "C++"
