@@ -19,7 +19,10 @@ serialization crosses the wire:
 
   C2 dictionary unification: each rank's string dictionary travels as a
      UTF-8 byte blob + offset tensor; every rank builds the global
-     dictionary and remaps its peers' string codes into it.
+     dictionary and remaps its peers' string codes into it
+     (unify_dictionaries: a dict loop on the host, or the
+     unify_strings kernels, ops/hip/unify_strings.h, on the gathered
+     blobs where they lie; DRAGNET_UNIFY_GPU chooses).
   C1 table exchange: each rank's table flattens to an int64 key-code
      matrix [n, nk] (per-element tag: int / string-id / f64-bits packed
      into a companion column) and an f64 value vector.  Payloads are
@@ -247,10 +250,11 @@ def _group_rows_host(parts, remaps, nk):
         rc = _np(codes).reshape(rt.shape[0], nk).astype(np.int64,
                                                         copy=True)
         if remaps is not None:
+            remap = _np(remaps[r])  # a device slice after a GPU unify
             for j in range(nk):
                 is_str = ((rt >> (2 * j)) & 3) == _EL_STR
                 if is_str.any():
-                    rc[is_str, j] = remaps[r][rc[is_str, j]]
+                    rc[is_str, j] = remap[rc[is_str, j]]
         all_rows.append(np.concatenate([rc, rt[:, None]], axis=1))
         all_vals.append(_np(vals).astype(np.float64, copy=False))
     return _group_host(np.concatenate(all_rows), np.concatenate(all_vals))
@@ -287,9 +291,13 @@ def _group_rows_device(parts, remaps, nk, device):
         def offsets(sizes):
             return torch.from_numpy(
                 np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64))
+        if any(torch.is_tensor(m) for m in remaps):  # after a GPU unify
+            remap = torch.cat([up(m, torch.int64) for m in remaps])
+        else:
+            remap = up(np.concatenate(remaps), torch.int64)
         kw = dict(
             seg_start=offsets([int(_t.shape[0]) for _c, _t, _v in parts]),
-            remap=up(np.concatenate(remaps), torch.int64),
+            remap=remap,
             remap_off=offsets([len(m) for m in remaps]))
     uniq, sums, exact = ops.merge_rows(rows, vals, nk, sort=True, **kw)
     if not exact:
@@ -316,25 +324,54 @@ def _group_rows(parts, remaps, nk, device=None):
     return out
 
 
-def reaggregate(query, parts, strings_per_part, device=None):
-    """The step after the gather; needs no process group.  parts is
-    one (codes [n_r, nk], tagpack [n_r], vals [n_r]) per rank, numpy or
-    torch on any device, with string codes in that rank's dictionary
-    strings_per_part[r].  Builds the global dictionary (first seen
-    first, in rank order) and the per-rank remap tables on the host,
-    since strings are few; remaps, groups and sums the rows
-    (_group_rows: host or GPU, same result), and decodes the distinct
-    rows into the merged Aggregator, in np.unique's row order."""
-    nk = len(query.breakdowns)
-    if nk == 0:
-        vals = [_np(v).astype(np.float64, copy=False)
-                for _c, _t, v in parts]
-        return _scalar_table(
-            query, np.concatenate(vals) if vals else np.zeros(0))
+# ---- dictionary unification (C2) ----------------------------------------
+
+UNIFY_GPU_STRINGS_DEFAULT = float("inf")
+
+
+def _env_unify_gpu_strings():
+    """Total strings from which DRAGNET_UNIFY_GPU=auto unifies on the
+    GPU (DRAGNET_UNIFY_GPU_STRINGS).  The default is infinity: auto mode
+    never selects it, DRAGNET_UNIFY_GPU=1 does
+    (profiles/r10_unify_strings.md)."""
+    v = os.environ.get("DRAGNET_UNIFY_GPU_STRINGS")
+    if v is None:
+        return UNIFY_GPU_STRINGS_DEFAULT
+    try:
+        return int(v)
+    except ValueError:
+        return float("inf")
+
+
+def _is_blob_pair(d):
+    return isinstance(d, tuple) and len(d) == 2 and hasattr(d[0], "dtype")
+
+
+def _unify_on_gpu(dicts, n_strings):
+    """Path choice of the dictionary unification (DRAGNET_UNIFY_GPU),
+    with DRAGNET_MERGE_GPU's meaning: "0" always the host; "1" the GPU
+    whenever one is visible; "auto" the GPU from
+    DRAGNET_UNIFY_GPU_STRINGS strings up.  Dictionaries that arrive as
+    Python strings are on the host already and stay there."""
+    mode = os.environ.get("DRAGNET_UNIFY_GPU", "auto")
+    if mode == "0" or n_strings == 0:
+        return False
+    if not all(_is_blob_pair(d) for d in dicts):
+        return False
+    if mode != "1" and n_strings < _env_unify_gpu_strings():
+        return False
+    import torch
+    return torch.cuda.is_available()
+
+
+def _unify_host(dicts):
+    """The dict loop: the reference the device path must equal."""
     gdict = {}
     gstrings = []
     remaps = []
-    for rstr in strings_per_part:
+    for d in dicts:
+        rstr = _decode_strings(_np(d[0]).tobytes(), _np(d[1])) \
+            if _is_blob_pair(d) else d
         remap = np.empty(len(rstr), dtype=np.int64)
         for i, s in enumerate(rstr):
             gi = gdict.get(s)
@@ -343,6 +380,85 @@ def reaggregate(query, parts, strings_per_part, device=None):
                 gstrings.append(s)
             remap[i] = gi
         remaps.append(remap)
+    return gstrings, remaps
+
+
+def _unify_device(dicts, device):
+    """One unify_strings call (ops/hip/unify_strings.h) over the blobs
+    as one blob.  Blobs already on the GPU are never copied to the host;
+    the remap tables stay on the device, and only the bytes of the G
+    first occurrences come back, to be decoded into gstrings."""
+    import torch
+
+    from .ops import load_ops
+    ops = load_ops(required=True)  # a missing extension is an error
+    if device is None or torch.device(device).type != "cuda":
+        on_gpu = [d[0].device for d in dicts
+                  if torch.is_tensor(d[0]) and d[0].is_cuda]
+        device = on_gpu[0] if on_gpu else torch.device(
+            "cuda", torch.cuda.current_device())
+
+    def up(a, dtype):
+        return torch.as_tensor(a).to(device=device, dtype=dtype)
+
+    blobs = [up(b, torch.uint8).reshape(-1) for b, _o in dicts]
+    offs = [up(o, torch.int64).reshape(-1) for _b, o in dicts]
+    bases = np.concatenate(
+        [[0], np.cumsum([int(b.numel()) for b in blobs])])
+    counts = np.concatenate(
+        [[0], np.cumsum([max(int(o.numel()) - 1, 0) for o in offs])])
+    blob = torch.cat(blobs)
+    start = torch.cat([o[:-1] + int(bases[r]) for r, o in enumerate(offs)])
+    length = torch.cat([o[1:] - o[:-1] for o in offs])
+    remap, first = ops.unify_strings(blob, start, length)
+    remaps = [remap[int(counts[r]):int(counts[r + 1])]
+              for r in range(len(dicts))]
+    # the G distinct strings, packed in id order, are all that crosses
+    flen = length[first]
+    fend = torch.cumsum(flen, 0)
+    shift = start[first] - (fend - flen)  # source minus packed position
+    goffs = np.concatenate([[0], fend.cpu().numpy()])
+    nbytes = int(goffs[-1])
+    packed = blob[torch.repeat_interleave(shift, flen, output_size=nbytes)
+                  + torch.arange(nbytes, device=device)]
+    return _decode_strings(packed.cpu().numpy().tobytes(), goffs), remaps
+
+
+def unify_dictionaries(dicts, device=None):
+    """C2: one global dictionary out of the per-rank ones.  Each entry
+    of dicts is a list of str, or the wire form (blob uint8 [bytes],
+    offs int64 [n_r + 1]), numpy or torch on any device.  Returns
+    (gstrings, remaps): the distinct strings, first seen first in rank
+    order, and per rank the int64 table from its codes to indices of
+    gstrings.  On the host this is a dict loop over the decoded strings;
+    on the GPU (DRAGNET_UNIFY_GPU, wire-form entries only) the
+    unify_strings kernels number the spans where the gather left them,
+    the remaps stay device tensors for merge_rows, and only the distinct
+    strings are decoded.  Both give the same result."""
+    n_strings = sum(max(len(d[1]) - 1, 0) if _is_blob_pair(d) else len(d)
+                    for d in dicts)
+    if _unify_on_gpu(dicts, n_strings):
+        return _unify_device(dicts, device)
+    return _unify_host(dicts)
+
+
+def reaggregate(query, parts, strings_per_part, device=None):
+    """The step after the gather; needs no process group.  parts is
+    one (codes [n_r, nk], tagpack [n_r], vals [n_r]) per rank, numpy or
+    torch on any device, with string codes in that rank's dictionary
+    strings_per_part[r]: a list of str or a (blob, offs) pair.  Builds
+    the global dictionary (first seen first, in rank order) and the
+    per-rank remap tables (unify_dictionaries: host or GPU, same
+    result); remaps, groups and sums the rows (_group_rows: likewise),
+    and decodes the distinct rows into the merged Aggregator, in
+    np.unique's row order."""
+    nk = len(query.breakdowns)
+    if nk == 0:
+        vals = [_np(v).astype(np.float64, copy=False)
+                for _c, _t, v in parts]
+        return _scalar_table(
+            query, np.concatenate(vals) if vals else np.zeros(0))
+    gstrings, remaps = unify_dictionaries(strings_per_part, device)
     uniq, sums = _group_rows(parts, remaps, nk, device)
     return _decode_rows(query, uniq, sums, gstrings)
 
@@ -414,14 +530,13 @@ def merge_tables_tensor(agg, query, device=None, group=None):
         dev(np.frombuffer(blob, dtype=np.uint8).copy(), torch.uint8),
         list(ns_blob), device, group)
 
-    # C2 + C1: only the string blobs are decoded here; the gathered
-    # code, tag and value tensors go to reaggregate as they are
+    # C2 + C1: the gathered blobs, offsets, codes, tags and values go
+    # to reaggregate as they are; unify_dictionaries decodes the strings
+    # it needs
     strings_per_part = []
     parts = []
     for r in range(world):
-        sb = bytes(g_blob[r].cpu().numpy().tobytes())
-        strings_per_part.append(
-            _decode_strings(sb, g_soffs[r].cpu().numpy()))
+        strings_per_part.append((g_blob[r], g_soffs[r]))
         parts.append((g_codes[r].reshape(int(ns_rows[r]), nk),
                       g_tags[r], g_vals[r]))
     merged = reaggregate(query, parts, strings_per_part, device=device)
@@ -467,24 +582,13 @@ def _merge_partitioned(query, codes, tagpack, vals, strings, device,
     g_blob = _all_gather_padded(
         dev(np.frombuffer(blob, dtype=np.uint8).copy(), torch.uint8),
         list(metas[:, 1]), device, group)
-    gdict = {}
-    gstrings = []
-    remaps = []
-    for r in range(world):
-        sb = bytes(g_blob[r].cpu().numpy().tobytes())
-        rstr = _decode_strings(sb, g_soffs[r].cpu().numpy())
-        remap = np.empty(max(len(rstr), 1), dtype=np.int64)
-        for i, s in enumerate(rstr):
-            gi = gdict.get(s)
-            if gi is None:
-                gi = gdict[s] = len(gstrings)
-                gstrings.append(s)
-            remap[i] = gi
-        remaps.append(remap)
+    gstrings, remaps = unify_dictionaries(
+        [(g_blob[r], g_soffs[r]) for r in range(world)], device)
+    my_remap = _np(remaps[rank])
     for j in range(nk):
         is_str = ((tagpack >> (2 * j)) & 3) == _EL_STR
         if is_str.any():
-            codes[is_str, j] = remaps[rank][codes[is_str, j]]
+            codes[is_str, j] = my_remap[codes[is_str, j]]
 
     # partition rows by key hash
     h = np.zeros(codes.shape[0], dtype=np.uint64)

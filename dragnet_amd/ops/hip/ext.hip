@@ -447,6 +447,117 @@ std::tuple<torch::Tensor, torch::Tensor, bool> merge_rows(
                          !(status & MERGE_INEXACT));
 }
 
+// Number the distinct byte strings among the spans (start[i], length[i])
+// of blob in order of first occurrence (unify_strings.h): remap int64 [n]
+// is the id of string i, first int64 [g] the index of the first
+// occurrence of id g.  hash_mask narrows the hashes (tests); max_blocks >
+// 0 caps the grids of the hash and insert kernels.  n == 0 launches
+// nothing.  Syncs once, to learn g and whether every span lay inside the
+// blob.
+std::tuple<torch::Tensor, torch::Tensor> unify_strings(
+    torch::Tensor blob, torch::Tensor start, torch::Tensor length,
+    int64_t hash_mask, int64_t max_blocks) {
+  CHECK_GPU(blob);
+  CHECK_GPU(start);
+  CHECK_GPU(length);
+  TORCH_CHECK(blob.scalar_type() == torch::kUInt8 && blob.dim() == 1 &&
+                  blob.is_contiguous(),
+              "unify_strings: blob must be contiguous uint8 [bytes]");
+  const auto dev = blob.device();
+  TORCH_CHECK(start.scalar_type() == torch::kInt64 && start.dim() == 1 &&
+                  start.is_contiguous() && start.device() == dev,
+              "unify_strings: start must be contiguous int64 [n] on the "
+              "device of blob");
+  TORCH_CHECK(length.scalar_type() == torch::kInt64 && length.dim() == 1 &&
+                  length.is_contiguous() && length.device() == dev,
+              "unify_strings: length must be contiguous int64 [n] on the "
+              "device of blob");
+  const int64_t n = start.size(0);
+  TORCH_CHECK(length.size(0) == n, "unify_strings: start has ", n,
+              " entries, length has ", length.size(0));
+  TORCH_CHECK(n < ((int64_t)1 << 31), "unify_strings: n exceeds 2^31 spans");
+  TORCH_CHECK(max_blocks >= 0, "unify_strings: max_blocks is negative");
+  auto on_dev = [&](torch::ScalarType t) {
+    return torch::dtype(t).device(dev);
+  };
+  if (n == 0)
+    return std::make_tuple(torch::empty({0}, on_dev(torch::kInt64)),
+                           torch::empty({0}, on_dev(torch::kInt64)));
+
+  c10::DeviceGuard guard(dev);
+  // words and 16-byte units are taken at multiples of 8 and 16 from the
+  // base of blob
+  if ((uintptr_t)blob.data_ptr() % 16 != 0) blob = blob.clone();
+
+  // next power of two at or above 2n, floor 1024, at most 2^31 (> n)
+  int64_t slots = 1024;
+  while (slots < 2 * n && slots < ((int64_t)1 << 31)) slots *= 2;
+  const int64_t n8 = (n + 7) / 8 * 8;
+  const int64_t nsums = (n8 + SORT_SCAN_TILE - 1) / SORT_SCAN_TILE;
+  torch::Tensor table, hash, slot_of, scan, sums, remap, first, meta;
+  try {
+    table = torch::full({slots}, -1, on_dev(torch::kInt32));
+    hash = torch::empty({n}, on_dev(torch::kInt64));
+    slot_of = torch::empty({n}, on_dev(torch::kInt32));
+    scan = torch::empty({n8}, on_dev(torch::kInt32));
+    sums = torch::empty({nsums}, on_dev(torch::kInt32));
+    remap = torch::empty({n}, on_dev(torch::kInt64));
+    first = torch::empty({n}, on_dev(torch::kInt64));
+    meta = torch::zeros({2}, on_dev(torch::kInt32));  // g, status
+  } catch (const c10::OutOfMemoryError& e) {
+    std::string why = e.what_without_backtrace();
+    TORCH_CHECK(false, "cannot allocate the unify table (", slots,
+                " slots for ", n, " strings): device allocation failed (",
+                why.substr(0, why.find('\n')), ")");
+  }
+  uint32_t* meta_p = (uint32_t*)meta.data_ptr();
+  UnifyArgs A = {};
+  A.blob = (const uint8_t*)blob.data_ptr();
+  A.blob_len = blob.numel();
+  A.start = (const long long*)start.data_ptr();
+  A.length = (const long long*)length.data_ptr();
+  A.n = (uint32_t)n;
+  A.hash_mask = (uint64_t)hash_mask;
+  A.hash = (unsigned long long*)hash.data_ptr();
+  A.table = (uint32_t*)table.data_ptr();
+  A.slot_mask = (uint32_t)(slots - 1);
+  A.slot_of = (uint32_t*)slot_of.data_ptr();
+  A.status = meta_p + 1;
+
+  const int64_t tiles = (n + UNIFY_TILE - 1) / UNIFY_TILE;
+  int64_t blocks = std::min<int64_t>(tiles, GRID_CAP);
+  if (max_blocks > 0) blocks = std::min(blocks, max_blocks);
+  const uint32_t* table_p = A.table;
+  const uint32_t* slot_p = A.slot_of;
+  uint32_t* scan_p = (uint32_t*)scan.data_ptr();
+  uint32_t* sums_p = (uint32_t*)sums.data_ptr();
+  launch("unify_hash", unify_hash_kernel, dim3((uint32_t)blocks),
+         dim3(UNIFY_TILE), 0, A);
+  launch("unify_insert", unify_insert_kernel, dim3((uint32_t)blocks),
+         dim3(UNIFY_TILE), 0, A);
+  launch("unify_flag", unify_flag_kernel,
+         dim3((uint32_t)((n8 + UNIFY_TILE - 1) / UNIFY_TILE)),
+         dim3(UNIFY_TILE), 0, table_p, slot_p, (uint32_t)n, (uint32_t)n8,
+         (const uint32_t*)A.status, scan_p);
+  launch("sort_scan", sort_scan_kernel, dim3((uint32_t)nsums),
+         dim3(SORT_BLOCK), 0, scan_p, (uint32_t)n8, sums_p);
+  launch("sort_scan_sums", sort_scan_sums_kernel, dim3(1), dim3(SORT_BLOCK),
+         0, sums_p, (uint32_t)nsums);
+  launch("unify_emit", unify_emit_kernel, dim3((uint32_t)tiles),
+         dim3(UNIFY_TILE), 0, table_p, slot_p, (uint32_t)n,
+         (const uint32_t*)scan_p, (const uint32_t*)sums_p,
+         (const uint32_t*)A.status, (long long*)remap.data_ptr(),
+         (long long*)first.data_ptr(), meta_p);
+  auto host = meta.cpu();  // waits for the kernels
+  const int64_t g = host.data_ptr<int32_t>()[0];
+  const uint32_t status = (uint32_t)host.data_ptr<int32_t>()[1];
+  TORCH_CHECK(!(status & UNIFY_BAD_SPAN),
+              "unify_strings: a span lies outside the blob (a negative "
+              "start or length, or an end beyond ", blob.numel(), " bytes)");
+  TORCH_CHECK(!(status & UNIFY_FULL), "unify_strings: unify table full");
+  return std::make_tuple(remap, first.narrow(0, 0, g));
+}
+
 // The bound state of one scan context.  Built once from keyword
 // arguments; allocates and owns every tensor its PlanView / AggTable /
 // StrDict / NumDict descriptors point at, so their lifetime does not
@@ -997,6 +1108,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sort_rows", &dn::sort_rows, py::arg("rows"),
         "stable lexicographic sorting permutation (int32 [n]) of int64 "
         "rows [n, w] on the GPU");
+  m.def("unify_strings", &dn::unify_strings, py::arg("blob"),
+        py::arg("start"), py::arg("length"), py::arg("hash_mask") = -1,
+        py::arg("max_blocks") = 0,
+        "number the distinct byte strings among spans of a GPU blob in "
+        "order of first occurrence -> (remap int64 [n], first int64 [g])");
   m.def("lds_bytes", &dn::lds_bytes, py::arg("nf"), py::arg("nm"),
         py::arg("ns") = 0, py::arg("columnar") = false,
         "dynamic LDS bytes of a scan / columnar launch (host only)");
@@ -1034,5 +1150,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("grow_ndict", &dn::ScanState::grow_ndict, py::arg("new_slots"));
   m.attr("MAX_KEY") = (int)dn::MAX_KEY;
   m.attr("SORT_TILE") = (int)dn::SORT_TILE;
+  m.attr("UNIFY_TILE") = (int)dn::UNIFY_TILE;
+  m.attr("UNIFY_STAGE_BYTES") = (int)dn::UNIFY_STAGE_BYTES;
   m.attr("MAX_FIELDS") = (int)dn::MAX_FIELDS;
 }

@@ -20,7 +20,8 @@
 // scan_rehash.h (device only: table growth between launches),
 // scan_columns.h (device only: the index queries over typed columns),
 // merge_rows.h (device only: re-aggregation of merged multi-GPU tables),
-// sort_rows.h (device only: radix sort of the merged rows).
+// sort_rows.h (device only: radix sort of the merged rows),
+// unify_strings.h (device only: one dictionary out of the ranks').
 
 #include "common.h"
 #include <hip/hip_runtime.h>
@@ -601,5 +602,8 @@ __global__ void extract_numdict_kernel(NumDict D, double* out_vals,
 
 // radix sort of the merged rows into np.unique's order; last again
 #include "sort_rows.h"
+
+// first-occurrence numbering of the ranks' dictionary strings; last again
+#include "unify_strings.h"
 
 }  // extern "C++"
