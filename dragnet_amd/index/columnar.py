@@ -42,6 +42,7 @@ import struct
 
 import numpy as np
 
+from ..merge import FirstSeen
 from .query import (IndexError_, check_version, column_kinds, find_metric,
                     metric_entry)
 from .sink import sqlite3_escape
@@ -555,7 +556,8 @@ def merge_group(members, needed, max_rows=MAX_ROWS,
                                  if kinds[n] == "s"}
             parts = {n: [] for n in needed}
             parts["value"] = []
-            where = {}
+            where = FirstSeen()
+            cur.dict_values = where.values
             nbytes = 0
         cur.members.append(sc)
         parts["value"].append(vals)
@@ -565,14 +567,8 @@ def merge_group(members, needed, max_rows=MAX_ROWS,
                 parts[n].append(loaded[n])
                 continue
             codes, values = loaded[n]
-            # the launch dictionary: a dict over the DISTINCT values
-            remap = np.zeros(len(values), dtype=np.uint32)
-            for i, v in enumerate(values):
-                g = where.get(v)
-                if g is None:
-                    g = where[v] = len(cur.dict_values)
-                    cur.dict_values.append(v)
-                remap[i] = g
+            # the launch dictionary numbers the DISTINCT values
+            remap = where.ids(values).astype(np.uint32)
             parts[n].append(remap[codes] if len(codes)
                             else np.zeros(0, dtype=np.uint32))
             if infos[n].get("has_backslash") or any(

@@ -1,0 +1,393 @@
+"""
+The step after the multi-GPU gather: re-aggregate the ranks' tables.
+Nothing here needs a process group; distributed.py does the collectives
+and hands the gathered tensors to reaggregate().
+
+  wire form: a rank's table is an int64 key-code matrix [n, nk], a tag
+     column (2 bits per element: int / string-id / f64-bits) and an f64
+     value vector (_encode_table); its string dictionary is a UTF-8 byte
+     blob + offset array (_strings_blob).
+  C2 unify_dictionaries: the global dictionary, first seen first in rank
+     order, and per rank the table from its codes to global ones:
+     FirstSeen on the host, or the unify_strings kernels
+     (ops/hip/unify_strings.h) on the gathered blobs where they lie.
+  C1 _group_rows: remap the string codes, group identical rows and sum
+     their values: np.unique + bincount on the host, or the merge_rows
+     kernels (ops/hip/merge_rows.h, ordered by sort_rows.h).
+  DRAGNET_UNIFY_GPU and DRAGNET_MERGE_GPU choose (_use_gpu); the host
+  and device paths give the same bits.
+"""
+
+import os
+
+import numpy as np
+
+from .points import Aggregator
+
+# per-element tag values in the packed tag column
+_EL_INT = 0   # int64 payload (ordinals, dates, integral counts)
+_EL_STR = 1   # payload = index into the rank's string dictionary
+_EL_F64 = 2   # payload = IEEE-754 bits of a float key element
+
+
+# ---- dense table encode/decode ----------------------------------------
+
+def _encode_table(agg, nk):
+    """Flatten an Aggregator's table to dense arrays:
+    (codes i64 [n, nk], tagpack i64 [n], vals f64 [n], strings list).
+    Key elements are int (ordinal/date), str, or (defensively) float;
+    strings are dictionary-encoded per rank (C2 unifies them)."""
+    n = len(agg.table)
+    codes = np.zeros((n, nk), dtype=np.int64)
+    tagpack = np.zeros(n, dtype=np.int64)
+    vals = np.empty(n, dtype=np.float64)
+    strings = []
+    sidx = {}
+    for i, (k, v) in enumerate(agg.table.items()):
+        vals[i] = v
+        tp = 0
+        for j, el in enumerate(k):
+            if isinstance(el, str):
+                si = sidx.get(el)
+                if si is None:
+                    si = sidx[el] = len(strings)
+                    strings.append(el)
+                codes[i, j] = si
+                tp |= _EL_STR << (2 * j)
+            elif isinstance(el, float) and not el.is_integer():
+                codes[i, j] = np.float64(el).view(np.int64)
+                tp |= _EL_F64 << (2 * j)
+            else:
+                iv = int(el)
+                if -(1 << 63) <= iv < (1 << 63):
+                    codes[i, j] = iv
+                else:
+                    # lquantize ordinals of absurd magnitudes exceed
+                    # int64: ship as f64 bits (JS-float key semantics
+                    # — the reference's ordinals are floats there
+                    # anyway); every rank rebuilds the same float key
+                    codes[i, j] = np.float64(float(iv)).view(np.int64)
+                    tp |= _EL_F64 << (2 * j)
+        tagpack[i] = tp
+    return codes, tagpack, vals, strings
+
+
+def _strings_blob(strings):
+    bs = [s.encode("utf-8") for s in strings]
+    offs = np.zeros(len(bs) + 1, dtype=np.int64)
+    if bs:
+        np.cumsum([len(b) for b in bs], out=offs[1:])
+    return b"".join(bs), offs
+
+
+def _decode_strings(blob_bytes, offs):
+    return [blob_bytes[offs[i]:offs[i + 1]].decode("utf-8")
+            for i in range(len(offs) - 1)]
+
+
+def _group_host(X, vals):
+    """Group identical rows of X [n, w] and sum vals over each group:
+    (uniq [g, w] in np.unique's order, sums f64 [g])."""
+    uniq, inv = np.unique(X, axis=0, return_inverse=True)
+    sums = np.bincount(inv, weights=vals, minlength=uniq.shape[0])
+    return uniq, sums
+
+
+def _scalar_table(query, vals):
+    """The table of a query without breakdowns: one scalar sum."""
+    merged = Aggregator(query)
+    if vals.size:
+        total = float(vals.sum())
+        merged.table[()] = int(total) if total.is_integer() else total
+    return merged
+
+
+def _decode_rows(query, uniq, sums, strings):
+    """Decode each UNIQUE key row [codes..., tagpack] to the
+    Aggregator's canonical Python tuple once, in row order."""
+    merged = Aggregator(query)
+    nk = len(query.breakdowns)
+    for r in range(uniq.shape[0]):
+        tp = int(uniq[r, nk])
+        key = []
+        for j in range(nk):
+            tag = (tp >> (2 * j)) & 3
+            c = int(uniq[r, j])
+            if tag == _EL_STR:
+                key.append(strings[c])
+            elif tag == _EL_F64:
+                key.append(float(np.int64(c).view(np.float64)))
+            else:
+                key.append(c)
+        v = float(sums[r])
+        merged.table[tuple(key)] = int(v) if v.is_integer() else v
+    return merged
+
+
+def _rebuild_table(query, codes, tagpack, vals, strings):
+    """Vectorized host re-aggregation of one dense table: group
+    identical key rows with np.unique and sum values with bincount
+    (_group_host), then decode the unique rows (_decode_rows).  The
+    per-row Python of _encode_table and of the decode loop is what it
+    was; vectorising either is a separate piece of work."""
+    if len(query.breakdowns) == 0:
+        return _scalar_table(query, vals)
+    X = np.concatenate([codes, tagpack[:, None]], axis=1)
+    return _decode_rows(query, *_group_host(X, vals), strings)
+
+
+# ---- what the host and device paths share ------------------------------
+
+def _use_gpu(mode_var, threshold_var, count):
+    """The path policy of both device steps.  Mode "0": never the GPU;
+    "1": whenever one is visible; anything else ("auto", the default):
+    from `threshold_var` items up, where unset or unparsable means
+    infinity: auto then never selects it.  No items: the host."""
+    mode = os.environ.get(mode_var, "auto")
+    if mode == "0" or count == 0:
+        return False
+    if mode != "1":
+        try:
+            threshold = int(os.environ[threshold_var])
+        except (KeyError, ValueError):
+            threshold = float("inf")
+        if count < threshold:
+            return False
+    import torch
+    return torch.cuda.is_available()
+
+
+def _np(a):
+    return a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+
+
+def _work_device(device, inputs):
+    """(device, up): the CUDA device a device step works on (`device`
+    if it is one, else that of the first input already on a GPU, else
+    the current one) and up(a, dtype), which puts an array or tensor
+    there.  Inputs already on it are not copied."""
+    import torch
+    if device is None or torch.device(device).type != "cuda":
+        on_gpu = [t.device for t in inputs
+                  if torch.is_tensor(t) and t.is_cuda]
+        device = on_gpu[0] if on_gpu else torch.device(
+            "cuda", torch.cuda.current_device())
+
+    def up(a, dtype):
+        return torch.as_tensor(a).to(device=device, dtype=dtype)
+
+    return device, up
+
+
+class FirstSeen:
+    """Numbers byte strings in order of first occurrence: the host form
+    of ops/hip/unify_strings.h.  `values` is the running dictionary."""
+
+    def __init__(self):
+        self.values = []
+        self._where = {}
+
+    def ids(self, items):
+        """int64 ids of items (bytes each); the unseen ones are appended
+        to the dictionary in order."""
+        where, values = self._where, self.values
+        out = np.empty(len(items), dtype=np.int64)
+        for i, v in enumerate(items):
+            g = where.get(v)
+            if g is None:
+                g = where[v] = len(values)
+                values.append(v)
+            out[i] = g
+        return out
+
+
+# ---- row grouping (C1) ---------------------------------------------------
+
+def _merge_on_gpu(n_rows, nk):
+    """Path choice of the row grouping: _use_gpu over DRAGNET_MERGE_GPU
+    and DRAGNET_MERGE_GPU_ROWS total rows.  profiles/r08_merge_rows.md
+    measured no size that wins at every cardinality, hence infinity;
+    with the rows ordered on the device (profiles/r09_sort_rows.md) the
+    same rule gives 10000, and the default is unchanged so far.  A table
+    without breakdowns is a scalar sum and stays on the host."""
+    return nk >= 1 and _use_gpu("DRAGNET_MERGE_GPU",
+                                "DRAGNET_MERGE_GPU_ROWS", n_rows)
+
+
+def _group_rows_host(parts, remaps, nk):
+    """Remap (numpy fancy indexing), concatenate, group: the reference
+    the device path must equal bit for bit."""
+    all_rows, all_vals = [], []
+    for r, (codes, tags, vals) in enumerate(parts):
+        rt = _np(tags).astype(np.int64, copy=False)
+        rc = _np(codes).reshape(rt.shape[0], nk).astype(np.int64,
+                                                        copy=True)
+        if remaps is not None:
+            remap = _np(remaps[r])  # a device slice after a GPU unify
+            for j in range(nk):
+                is_str = ((rt >> (2 * j)) & 3) == _EL_STR
+                if is_str.any():
+                    rc[is_str, j] = remap[rc[is_str, j]]
+        all_rows.append(np.concatenate([rc, rt[:, None]], axis=1))
+        all_vals.append(_np(vals).astype(np.float64, copy=False))
+    return _group_host(np.concatenate(all_rows), np.concatenate(all_vals))
+
+
+def _group_rows_device(parts, remaps, nk, device):
+    """One merge_rows call over the parts as segments; the remap runs
+    inside the kernel.  Parts already on the GPU are never copied to
+    the host; only the distinct rows and their sums come back, already
+    in np.unique's order (lexicographic over the columns left to right,
+    as signed int64: the radix sort of ops/hip/sort_rows.h, behind
+    merge_rows' sort=True).  None when the kernel reports sums that
+    depend on the order of its adds."""
+    import torch
+
+    from .ops import load_ops
+    ops = load_ops(required=True)  # a missing extension is an error
+    device, up = _work_device(device, [p[0] for p in parts])
+    rows = torch.cat([
+        torch.cat([up(codes, torch.int64).reshape(-1, nk),
+                   up(tags, torch.int64).reshape(-1, 1)], dim=1)
+        for codes, tags, _vals in parts])
+    vals = torch.cat([up(v, torch.float64) for _c, _t, v in parts])
+    kw = {}
+    if remaps is not None:
+        def offsets(sizes):
+            return torch.from_numpy(
+                np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64))
+        if any(torch.is_tensor(m) for m in remaps):  # after a GPU unify
+            remap = torch.cat([up(m, torch.int64) for m in remaps])
+        else:
+            remap = up(np.concatenate(remaps), torch.int64)
+        kw = dict(
+            seg_start=offsets([int(_t.shape[0]) for _c, _t, _v in parts]),
+            remap=remap,
+            remap_off=offsets([len(m) for m in remaps]))
+    uniq, sums, exact = ops.merge_rows(rows, vals, nk, sort=True, **kw)
+    if not exact:
+        return None
+    return uniq.cpu().numpy(), sums.cpu().numpy()
+
+
+def _group_rows(parts, remaps, nk, device=None):
+    """Group the rows [codes..., tagpack] of all parts and sum their
+    values: (uniq [g, nk + 1], sums [g]) in np.unique's order.  remaps
+    is one int64 table per part for its string-tagged codes, or None.
+
+    The result is bit-identical whichever path runs.  Device f64 adds
+    come in no fixed order, and only sums of non-negative integers that
+    stay below 2^53 are independent of the order, so the kernel reports
+    anything else (a fractional, negative, NaN or infinite weight, a
+    value or a sum at or beyond 2^53) and the host path then answers."""
+    n_rows = sum(int(p[1].shape[0]) for p in parts)
+    out = None
+    if _merge_on_gpu(n_rows, nk):
+        out = _group_rows_device(parts, remaps, nk, device)
+    if out is None:
+        out = _group_rows_host(parts, remaps, nk)
+    return out
+
+
+# ---- dictionary unification (C2) ----------------------------------------
+
+def _is_blob_pair(d):
+    return isinstance(d, tuple) and len(d) == 2 and hasattr(d[0], "dtype")
+
+
+def _unify_on_gpu(dicts, n_strings):
+    """Path choice of the dictionary unification: _use_gpu over
+    DRAGNET_UNIFY_GPU and DRAGNET_UNIFY_GPU_STRINGS total strings
+    (infinity by default: profiles/r10_unify_strings.md).  Dictionaries
+    that arrive as Python strings are on the host already and stay
+    there."""
+    return all(_is_blob_pair(d) for d in dicts) and _use_gpu(
+        "DRAGNET_UNIFY_GPU", "DRAGNET_UNIFY_GPU_STRINGS", n_strings)
+
+
+def _unify_host(dicts):
+    """FirstSeen over the strings' UTF-8 bytes (the encoding is
+    one-to-one): the reference the device path must equal.  Wire-form
+    entries are sliced, not decoded; only the distinct strings are."""
+    seen = FirstSeen()
+    remaps = []
+    for d in dicts:
+        if _is_blob_pair(d):
+            blob, offs = _np(d[0]).tobytes(), _np(d[1]).tolist()
+            items = [blob[a:b] for a, b in zip(offs, offs[1:])]
+        else:
+            items = [s.encode("utf-8") for s in d]
+        remaps.append(seen.ids(items))
+    return [b.decode("utf-8") for b in seen.values], remaps
+
+
+def _unify_device(dicts, device):
+    """One unify_strings call (ops/hip/unify_strings.h) over the blobs
+    as one blob.  Blobs already on the GPU are never copied to the host;
+    the remap tables stay on the device, and only the bytes of the G
+    first occurrences come back, to be decoded into gstrings."""
+    import torch
+
+    from .ops import load_ops
+    ops = load_ops(required=True)  # a missing extension is an error
+    device, up = _work_device(device, [d[0] for d in dicts])
+    blobs = [up(b, torch.uint8).reshape(-1) for b, _o in dicts]
+    offs = [up(o, torch.int64).reshape(-1) for _b, o in dicts]
+    bases = np.concatenate(
+        [[0], np.cumsum([int(b.numel()) for b in blobs])])
+    counts = np.concatenate(
+        [[0], np.cumsum([max(int(o.numel()) - 1, 0) for o in offs])])
+    blob = torch.cat(blobs)
+    start = torch.cat([o[:-1] + int(bases[r]) for r, o in enumerate(offs)])
+    length = torch.cat([o[1:] - o[:-1] for o in offs])
+    remap, first = ops.unify_strings(blob, start, length)
+    remaps = [remap[int(counts[r]):int(counts[r + 1])]
+              for r in range(len(dicts))]
+    # the G distinct strings, packed in id order, are all that crosses
+    flen = length[first]
+    fend = torch.cumsum(flen, 0)
+    shift = start[first] - (fend - flen)  # source minus packed position
+    goffs = np.concatenate([[0], fend.cpu().numpy()])
+    nbytes = int(goffs[-1])
+    packed = blob[torch.repeat_interleave(shift, flen, output_size=nbytes)
+                  + torch.arange(nbytes, device=device)]
+    return _decode_strings(packed.cpu().numpy().tobytes(), goffs), remaps
+
+
+def unify_dictionaries(dicts, device=None):
+    """C2: one global dictionary out of the per-rank ones.  Each entry
+    of dicts is a list of str, or the wire form (blob uint8 [bytes],
+    offs int64 [n_r + 1]), numpy or torch on any device.  Returns
+    (gstrings, remaps): the distinct strings, first seen first in rank
+    order, and per rank the int64 table from its codes to indices of
+    gstrings.  On the host this is FirstSeen over the strings' bytes;
+    on the GPU (DRAGNET_UNIFY_GPU, wire-form entries only) the
+    unify_strings kernels number the spans where the gather left them
+    and the remaps stay device tensors for merge_rows.  Either way only
+    the distinct strings are decoded, and both give the same result."""
+    n_strings = sum(max(len(d[1]) - 1, 0) if _is_blob_pair(d) else len(d)
+                    for d in dicts)
+    if _unify_on_gpu(dicts, n_strings):
+        return _unify_device(dicts, device)
+    return _unify_host(dicts)
+
+
+def reaggregate(query, parts, strings_per_part, device=None):
+    """The step after the gather; needs no process group.  parts is
+    one (codes [n_r, nk], tagpack [n_r], vals [n_r]) per rank, numpy or
+    torch on any device, with string codes in that rank's dictionary
+    strings_per_part[r]: a list of str or a (blob, offs) pair.  Builds
+    the global dictionary (first seen first, in rank order) and the
+    per-rank remap tables (unify_dictionaries: host or GPU, same
+    result); remaps, groups and sums the rows (_group_rows: likewise),
+    and decodes the distinct rows into the merged Aggregator, in
+    np.unique's row order."""
+    nk = len(query.breakdowns)
+    if nk == 0:
+        vals = [_np(v).astype(np.float64, copy=False)
+                for _c, _t, v in parts]
+        return _scalar_table(
+            query, np.concatenate(vals) if vals else np.zeros(0))
+    gstrings, remaps = unify_dictionaries(strings_per_part, device)
+    uniq, sums = _group_rows(parts, remaps, nk, device)
+    return _decode_rows(query, uniq, sums, gstrings)

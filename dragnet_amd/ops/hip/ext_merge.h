@@ -1,0 +1,379 @@
+// Host bindings of the merge layer, the step after the multi-GPU gather
+// (dragnet_amd/merge.py): sort_rows (sort_rows.h), merge_rows
+// (merge_rows.h) and unify_strings (unify_strings.h), free functions
+// that keep nothing between calls.  Part of ext.hip's translation unit,
+// behind its launch plumbing (launch, on_dev, allocating, GRID_CAP).
+#pragma once
+
+namespace dn {
+
+namespace {
+
+// An argument of these bindings: a contiguous tensor of this dtype and
+// rank on the GPU `dev` (its own device, for a function's first).
+void check_arg(const char* fn, const char* name, const torch::Tensor& t,
+               torch::ScalarType dtype, int64_t rank, torch::Device dev) {
+  TORCH_CHECK(t.is_cuda() && t.device() == dev && t.scalar_type() == dtype &&
+                  t.dim() == rank && t.is_contiguous(),
+              fn, ": ", name, " must be a contiguous ", dtype, " tensor of "
+              "rank ", rank, " on the GPU of the first argument");
+}
+
+// Slots of a table for n keys: the next power of two at or above 2n,
+// floor 1024, at most 2^31 (> n), the most a uint32 slot addresses.
+int64_t table_slots(int64_t n) {
+  int64_t slots = 1024;
+  while (slots < 2 * n && slots < ((int64_t)1 << 31)) slots *= 2;
+  return slots;
+}
+
+uint32_t sort_span_grid(int64_t n) {
+  return (uint32_t)std::min<int64_t>((n + SORT_BLOCK - 1) / SORT_BLOCK,
+                                     GRID_CAP);
+}
+
+// The passes of the row sort (sort_rows.h) on the current stream: the
+// stable permutation that orders rows [n, w], n >= 2, as int32 [n].
+// span_dev is what sort_span_kernel left (AND words, then OR words);
+// span_host is the same on the host and is needed only for n >
+// SORT_TILE, where the host lists the passes.  Never syncs.
+torch::Tensor sort_passes(const long long* rows, int64_t n, int w,
+                          const unsigned long long* span_dev,
+                          const unsigned long long* span_host,
+                          torch::Device dev) {
+  const auto i32 = on_dev(dev, torch::kInt32);
+  struct Column { int c; int nshift; int shift[8]; };
+  Column cols[MERGE_W];
+  int ncols = 0;
+  if (n > SORT_TILE) {
+    for (int c = w - 1; c >= 0; c--) {
+      const unsigned long long diff = span_host[w + c] ^ span_host[c];
+      Column col = {c, 0, {}};
+      for (int b = 0; b < 8; b++)
+        if ((diff >> (8 * b)) & 0xffull) col.shift[col.nshift++] = 8 * b;
+      if (col.nshift) cols[ncols++] = col;
+    }
+    if (ncols == 0) return torch::arange(n, i32);
+  }
+  const int64_t ntiles = (n + SORT_TILE - 1) / SORT_TILE;
+  const int64_t total = ntiles * SORT_BINS;
+  const int64_t nsums = (total + SORT_SCAN_TILE - 1) / SORT_SCAN_TILE;
+  torch::Tensor key[2], idx[2], hist, sums;
+  allocating([&] {
+    idx[0] = torch::empty({n}, i32);
+    if (n > SORT_TILE) {
+      idx[1] = torch::empty({n}, i32);
+      key[0] = torch::empty({n}, on_dev(dev, torch::kInt64));
+      key[1] = torch::empty({n}, on_dev(dev, torch::kInt64));
+      hist = torch::empty({total}, i32);
+      sums = torch::empty({nsums}, i32);
+    }
+  }, "cannot allocate the sort buffers (two key and two index arrays and "
+     "the histograms for ", n, " rows)");
+  if (n <= SORT_TILE) {
+    launch("sort_small", sort_small_kernel, dim3(1), dim3(SORT_BLOCK), 0,
+           rows, (uint32_t)n, w, span_dev, (uint32_t*)idx[0].data_ptr());
+    return idx[0];
+  }
+  sort_key_t* kp[2] = {(sort_key_t*)key[0].data_ptr(),
+                       (sort_key_t*)key[1].data_ptr()};
+  uint32_t* ip[2] = {(uint32_t*)idx[0].data_ptr(),
+                     (uint32_t*)idx[1].data_ptr()};
+  uint32_t* hp = (uint32_t*)hist.data_ptr();
+  uint32_t* sp = (uint32_t*)sums.data_ptr();
+  int cur = 0;
+  for (int i = 0; i < ncols; i++) {
+    launch("sort_key", sort_key_kernel,
+           dim3((uint32_t)((n + SORT_BLOCK - 1) / SORT_BLOCK)),
+           dim3(SORT_BLOCK), 0, rows, (uint32_t)n, w, cols[i].c,
+           i == 0 ? (const uint32_t*)nullptr : (const uint32_t*)ip[cur],
+           kp[cur], ip[cur]);
+    for (int j = 0; j < cols[i].nshift; j++) {
+      const int shift = cols[i].shift[j];
+      launch("sort_hist", sort_hist_kernel, dim3((uint32_t)ntiles),
+             dim3(SORT_BLOCK), 0, (const sort_key_t*)kp[cur], (uint32_t)n,
+             shift, hp, (uint32_t)ntiles);
+      launch("sort_scan", sort_scan_kernel, dim3((uint32_t)nsums),
+             dim3(SORT_BLOCK), 0, hp, (uint32_t)total, sp);
+      launch("sort_scan_sums", sort_scan_sums_kernel, dim3(1),
+             dim3(SORT_BLOCK), 0, sp, (uint32_t)nsums);
+      launch("sort_scatter", sort_scatter_kernel, dim3((uint32_t)ntiles),
+             dim3(SORT_BLOCK), 0, (const sort_key_t*)kp[cur],
+             (const uint32_t*)ip[cur], kp[cur ^ 1], ip[cur ^ 1],
+             (uint32_t)n, shift, (const uint32_t*)hp, (const uint32_t*)sp,
+             (uint32_t)ntiles);
+      cur ^= 1;
+    }
+  }
+  return idx[cur];
+}
+
+}  // namespace
+
+// The stable permutation that sorts the rows of a contiguous int64
+// [n, w] GPU tensor lexicographically, column 0 first, each word as a
+// signed int64: np.lexsort(rows.T[::-1]), as int32 [n] (sort_rows.h).
+// n < 2 launches nothing; n <= SORT_TILE never syncs; beyond that it
+// syncs once, to read which bytes vary, and returns the identity with no
+// pass when none does.
+torch::Tensor sort_rows(torch::Tensor rows) {
+  const auto dev = rows.device();
+  check_arg("sort_rows", "rows", rows, torch::kInt64, 2, dev);
+  TORCH_CHECK(rows.size(1) >= 1 && rows.size(1) <= MERGE_W,
+              "sort_rows: rows must be [n, w] with w in 1..", (int)MERGE_W);
+  const int64_t n = rows.size(0);
+  const int w = (int)rows.size(1);
+  TORCH_CHECK(n < ((int64_t)1 << 31), "sort_rows: n exceeds 2^31 rows");
+  if (n < 2) return torch::zeros({n}, on_dev(dev, torch::kInt32));
+
+  c10::DeviceGuard guard(dev);
+  auto span = torch::zeros({2 * w}, on_dev(dev, torch::kInt64));
+  span.narrow(0, 0, w).fill_(-1);
+  const long long* rp = (const long long*)rows.data_ptr();
+  unsigned long long* span_p = (unsigned long long*)span.data_ptr();
+  launch("sort_span", sort_span_kernel, dim3(sort_span_grid(n)),
+         dim3(SORT_BLOCK), 0, rp, (uint32_t)n, (const uint32_t*)nullptr, w,
+         span_p);
+  if (n <= SORT_TILE) return sort_passes(rp, n, w, span_p, nullptr, dev);
+  auto host = span.cpu();  // waits for the span
+  return sort_passes(rp, n, w, span_p,
+                     (const unsigned long long*)host.data_ptr(), dev);
+}
+
+// Group identical rows and sum their values (merge_rows.h): rows is
+// int64 [n, nk + 1] (key codes, then the tag pack), vals f64 [n].  With
+// seg_start / remap / remap_off the rows come in segments, each with a
+// remap table for its string-tagged codes (remap concatenated, the
+// tables delimited by remap_off); the three go together.  Returns the g
+// distinct rows (any order), their sums, and whether the sums are exact:
+// if not they depend on the order of the device's adds, and the caller
+// must not use them.  hash_mask narrows the home slots (tests);
+// max_blocks > 0 caps the grid.  With sort the rows and sums come back
+// in np.unique's order (sort_rows.h): the span kernel runs behind the
+// compaction on the device-side count, its words come back in the copy
+// that fetches g, and the sort passes are enqueued after it.  Syncs
+// once either way, to learn g.
+std::tuple<torch::Tensor, torch::Tensor, bool> merge_rows(
+    torch::Tensor rows, torch::Tensor vals, int64_t nk,
+    c10::optional<torch::Tensor> seg_start,
+    c10::optional<torch::Tensor> remap,
+    c10::optional<torch::Tensor> remap_off, int64_t hash_mask,
+    int64_t max_blocks, bool sort) {
+  const auto dev = rows.device();
+  TORCH_CHECK(nk >= 1 && nk <= MAX_KEY, "merge_rows: nk must be 1..",
+              (int)MAX_KEY);
+  const int64_t w = nk + 1;
+  check_arg("merge_rows", "rows", rows, torch::kInt64, 2, dev);
+  TORCH_CHECK(rows.size(1) == w, "merge_rows: rows must be [n, nk + 1]");
+  const int64_t n = rows.size(0);
+  check_arg("merge_rows", "vals", vals, torch::kFloat64, 1, dev);
+  TORCH_CHECK(vals.size(0) == n, "merge_rows: rows has ", n,
+              " rows, vals has ", vals.size(0));
+  TORCH_CHECK(n < ((int64_t)1 << 31), "merge_rows: n exceeds 2^31 rows");
+  TORCH_CHECK(max_blocks >= 0, "merge_rows: max_blocks is negative");
+  const bool segmented = seg_start.has_value();
+  TORCH_CHECK(segmented == remap.has_value() &&
+                  segmented == remap_off.has_value(),
+              "merge_rows: seg_start, remap and remap_off go together");
+
+  const auto i64 = on_dev(dev, torch::kInt64);
+  const auto f64 = on_dev(dev, torch::kFloat64);
+  MergeArgs A = {};
+  torch::Tensor seg_dev, off_dev;
+  if (segmented) {
+    // the segment structure is a few entries per rank: validated on the
+    // host, since the kernel indexes remap through it
+    auto seg = seg_start->to(torch::kCPU, torch::kInt64).contiguous();
+    auto off = remap_off->to(torch::kCPU, torch::kInt64).contiguous();
+    TORCH_CHECK(seg.dim() == 1 && seg.numel() >= 2 &&
+                    off.dim() == 1 && off.numel() == seg.numel(),
+                "merge_rows: seg_start and remap_off need nseg + 1 "
+                "entries each");
+    check_arg("merge_rows", "remap", *remap, torch::kInt64, 1, dev);
+    const int64_t* sp = seg.data_ptr<int64_t>();
+    const int64_t* op = off.data_ptr<int64_t>();
+    const int64_t nseg = seg.numel() - 1;
+    TORCH_CHECK(sp[0] == 0 && op[0] == 0,
+                "merge_rows: seg_start and remap_off start at 0");
+    for (int64_t i = 0; i < nseg; i++)
+      TORCH_CHECK(sp[i] <= sp[i + 1] && op[i] <= op[i + 1],
+                  "merge_rows: seg_start and remap_off must not decrease");
+    TORCH_CHECK(sp[nseg] == n, "merge_rows: seg_start ends at ", sp[nseg],
+                ", rows has ", n);
+    TORCH_CHECK(op[nseg] == remap->numel(), "merge_rows: remap_off ends at ",
+                op[nseg], ", remap has ", remap->numel());
+    seg_dev = seg.to(torch::kInt32).to(dev);
+    off_dev = off.to(dev);
+    A.nseg = (uint32_t)nseg;
+    A.seg_start = (const uint32_t*)seg_dev.data_ptr();
+    A.remap = (const long long*)remap->data_ptr();
+    A.remap_off = (const long long*)off_dev.data_ptr();
+  }
+  if (n == 0)
+    return std::make_tuple(torch::empty({0, w}, i64), torch::empty({0}, f64),
+                           true);
+
+  c10::DeviceGuard guard(dev);
+  // a tile is loaded 16 bytes at a time from the base of rows
+  if ((uintptr_t)rows.data_ptr() % 16 != 0) rows = rows.clone();
+
+  const int64_t slots = table_slots(n);
+  torch::Tensor state, keys, sum, out_rows, out_sums, meta;
+  allocating([&] {
+    const auto i32 = on_dev(dev, torch::kInt32);
+    state = torch::zeros({slots}, i32);
+    keys = torch::zeros({slots * w}, i64);
+    sum = torch::zeros({slots}, f64);
+    out_rows = torch::empty({n, w}, i64);
+    out_sums = torch::empty({n}, f64);
+    // g, status; with sort the span behind them: AND words, OR words
+    meta = torch::zeros({2 + (sort ? 4 * w : 0)}, i32);
+    if (sort) meta.narrow(0, 2, 2 * w).fill_(-1);
+  }, "cannot allocate the merge table (", slots, " slots for ", n, " rows)");
+  uint32_t* meta_p = (uint32_t*)meta.data_ptr();
+  A.rows = (const long long*)rows.data_ptr();
+  A.vals = (const double*)vals.data_ptr();
+  A.n = (uint32_t)n;
+  A.hash_mask = (uint64_t)hash_mask;
+  A.T.state = (uint32_t*)state.data_ptr();
+  A.T.keys = (long long*)keys.data_ptr();
+  A.T.sum = (double*)sum.data_ptr();
+  A.T.slots = (uint32_t)slots;
+  A.T.w = (int)w;
+  A.status = meta_p + 1;
+
+  int64_t blocks = std::min<int64_t>((n + MERGE_TILE - 1) / MERGE_TILE,
+                                     GRID_CAP);
+  if (max_blocks > 0) blocks = std::min(blocks, max_blocks);
+  launch("merge_insert", merge_insert_kernel, dim3((uint32_t)blocks),
+         dim3(MERGE_TILE), 0, A);
+  launch("merge_compact", merge_compact_kernel,
+         dim3((uint32_t)((slots + 255) / 256)), dim3(256), 0, A.T,
+         (long long*)out_rows.data_ptr(), (double*)out_sums.data_ptr(),
+         meta_p, meta_p + 1);
+  unsigned long long* span_p = (unsigned long long*)(meta_p + 2);
+  if (sort)  // sized for n; reads g on the device and exits beyond it
+    launch("sort_span", sort_span_kernel, dim3(sort_span_grid(n)),
+           dim3(SORT_BLOCK), 0, (const long long*)out_rows.data_ptr(),
+           (uint32_t)n, (const uint32_t*)meta_p, (int)w, span_p);
+  auto host = meta.cpu();  // waits for the kernels
+  const int64_t g = host.data_ptr<int32_t>()[0];
+  const uint32_t status = (uint32_t)host.data_ptr<int32_t>()[1];
+  TORCH_CHECK(!(status & MERGE_BAD_CODE),
+              "merge_rows: a string-tagged code lies outside its segment's "
+              "remap table (seg_start / remap_off do not describe these "
+              "rows)");
+  TORCH_CHECK(!(status & MERGE_FULL), "merge_rows: merge table full");
+  if (sort && g > 1) {
+    auto perm = sort_passes(
+        (const long long*)out_rows.data_ptr(), g, (int)w, span_p,
+        (const unsigned long long*)(host.data_ptr<int32_t>() + 2), dev);
+    auto sorted_rows = torch::empty({g, w}, i64);
+    auto sorted_sums = torch::empty({g}, f64);
+    launch("sort_gather", sort_gather_kernel,
+           dim3((uint32_t)((g + MERGE_TILE - 1) / MERGE_TILE)),
+           dim3(MERGE_TILE), 0, (const long long*)out_rows.data_ptr(),
+           (const double*)out_sums.data_ptr(),
+           (const uint32_t*)perm.data_ptr(), (uint32_t)g, (int)w,
+           (long long*)sorted_rows.data_ptr(),
+           (double*)sorted_sums.data_ptr());
+    return std::make_tuple(sorted_rows, sorted_sums,
+                           !(status & MERGE_INEXACT));
+  }
+  return std::make_tuple(out_rows.narrow(0, 0, g), out_sums.narrow(0, 0, g),
+                         !(status & MERGE_INEXACT));
+}
+
+// Number the distinct byte strings among the spans (start[i], length[i])
+// of blob in order of first occurrence (unify_strings.h): remap int64 [n]
+// is the id of string i, first int64 [g] the index of the first
+// occurrence of id g.  hash_mask narrows the hashes (tests); max_blocks >
+// 0 caps the grids of the hash and insert kernels.  n == 0 launches
+// nothing.  Syncs once, to learn g and whether every span lay inside the
+// blob.
+std::tuple<torch::Tensor, torch::Tensor> unify_strings(
+    torch::Tensor blob, torch::Tensor start, torch::Tensor length,
+    int64_t hash_mask, int64_t max_blocks) {
+  const auto dev = blob.device();
+  check_arg("unify_strings", "blob", blob, torch::kUInt8, 1, dev);
+  check_arg("unify_strings", "start", start, torch::kInt64, 1, dev);
+  check_arg("unify_strings", "length", length, torch::kInt64, 1, dev);
+  const int64_t n = start.size(0);
+  TORCH_CHECK(length.size(0) == n, "unify_strings: start has ", n,
+              " entries, length has ", length.size(0));
+  TORCH_CHECK(n < ((int64_t)1 << 31), "unify_strings: n exceeds 2^31 spans");
+  TORCH_CHECK(max_blocks >= 0, "unify_strings: max_blocks is negative");
+  const auto i32 = on_dev(dev, torch::kInt32);
+  const auto i64 = on_dev(dev, torch::kInt64);
+  if (n == 0)
+    return std::make_tuple(torch::empty({0}, i64), torch::empty({0}, i64));
+
+  c10::DeviceGuard guard(dev);
+  // words and 16-byte units are taken at multiples of 8 and 16 from the
+  // base of blob
+  if ((uintptr_t)blob.data_ptr() % 16 != 0) blob = blob.clone();
+
+  const int64_t slots = table_slots(n);
+  const int64_t n8 = (n + 7) / 8 * 8;
+  const int64_t nsums = (n8 + SORT_SCAN_TILE - 1) / SORT_SCAN_TILE;
+  torch::Tensor table, hash, slot_of, scan, sums, remap, first, meta;
+  allocating([&] {
+    table = torch::full({slots}, -1, i32);
+    hash = torch::empty({n}, i64);
+    slot_of = torch::empty({n}, i32);
+    scan = torch::empty({n8}, i32);
+    sums = torch::empty({nsums}, i32);
+    remap = torch::empty({n}, i64);
+    first = torch::empty({n}, i64);
+    meta = torch::zeros({2}, i32);  // g, status
+  }, "cannot allocate the unify table (", slots, " slots for ", n,
+     " strings)");
+  uint32_t* meta_p = (uint32_t*)meta.data_ptr();
+  UnifyArgs A = {};
+  A.blob = (const uint8_t*)blob.data_ptr();
+  A.blob_len = blob.numel();
+  A.start = (const long long*)start.data_ptr();
+  A.length = (const long long*)length.data_ptr();
+  A.n = (uint32_t)n;
+  A.hash_mask = (uint64_t)hash_mask;
+  A.hash = (unsigned long long*)hash.data_ptr();
+  A.table = (uint32_t*)table.data_ptr();
+  A.slot_mask = (uint32_t)(slots - 1);
+  A.slot_of = (uint32_t*)slot_of.data_ptr();
+  A.status = meta_p + 1;
+
+  const int64_t tiles = (n + UNIFY_TILE - 1) / UNIFY_TILE;
+  int64_t blocks = std::min<int64_t>(tiles, GRID_CAP);
+  if (max_blocks > 0) blocks = std::min(blocks, max_blocks);
+  const uint32_t* table_p = A.table;
+  const uint32_t* slot_p = A.slot_of;
+  uint32_t* scan_p = (uint32_t*)scan.data_ptr();
+  uint32_t* sums_p = (uint32_t*)sums.data_ptr();
+  launch("unify_hash", unify_hash_kernel, dim3((uint32_t)blocks),
+         dim3(UNIFY_TILE), 0, A);
+  launch("unify_insert", unify_insert_kernel, dim3((uint32_t)blocks),
+         dim3(UNIFY_TILE), 0, A);
+  launch("unify_flag", unify_flag_kernel,
+         dim3((uint32_t)((n8 + UNIFY_TILE - 1) / UNIFY_TILE)),
+         dim3(UNIFY_TILE), 0, table_p, slot_p, (uint32_t)n, (uint32_t)n8,
+         (const uint32_t*)A.status, scan_p);
+  launch("sort_scan", sort_scan_kernel, dim3((uint32_t)nsums),
+         dim3(SORT_BLOCK), 0, scan_p, (uint32_t)n8, sums_p);
+  launch("sort_scan_sums", sort_scan_sums_kernel, dim3(1), dim3(SORT_BLOCK),
+         0, sums_p, (uint32_t)nsums);
+  launch("unify_emit", unify_emit_kernel, dim3((uint32_t)tiles),
+         dim3(UNIFY_TILE), 0, table_p, slot_p, (uint32_t)n,
+         (const uint32_t*)scan_p, (const uint32_t*)sums_p,
+         (const uint32_t*)A.status, (long long*)remap.data_ptr(),
+         (long long*)first.data_ptr(), meta_p);
+  auto host = meta.cpu();  // waits for the kernels
+  const int64_t g = host.data_ptr<int32_t>()[0];
+  const uint32_t status = (uint32_t)host.data_ptr<int32_t>()[1];
+  TORCH_CHECK(!(status & UNIFY_BAD_SPAN),
+              "unify_strings: a span lies outside the blob (a negative "
+              "start or length, or an end beyond ", blob.numel(), " bytes)");
+  TORCH_CHECK(!(status & UNIFY_FULL), "unify_strings: unify table full");
+  return std::make_tuple(remap, first.narrow(0, 0, g));
+}
+
+}  // namespace dn

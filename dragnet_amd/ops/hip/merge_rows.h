@@ -1,6 +1,6 @@
 // Row re-aggregation layer, DEVICE ONLY: group identical int64 rows and
 // sum their f64 values.  This is the step after the multi-GPU gather
-// (dragnet_amd/distributed.py, reaggregate): every rank holds the union
+// (dragnet_amd/merge.py, reaggregate): every rank holds the union
 // of the per-rank aggregate tables as dense rows [codes..., tagpack] and
 // needs the distinct rows with the sum of the values over each.
 //
@@ -61,7 +61,8 @@
 //    and then come back under it unseen.  The caller discards an inexact
 //    result.
 #pragma once
-#include "scan_columns.h"
+#include "common.h"
+#include "dev_util.h"
 
 namespace dn {
 
@@ -70,7 +71,7 @@ constexpr int MERGE_TILE = 256;          // rows per tile = threads
 constexpr int MERGE_CACHE = 1024;        // per-block (slot, sum) entries
 constexpr int MERGE_CACHE_PROBES = 4;
 constexpr uint32_t MERGE_NO_SLOT = 0xFFFFFFFFu;
-constexpr long long MERGE_EL_STR = 1;    // distributed.py _EL_STR
+constexpr long long MERGE_EL_STR = 1;    // merge.py _EL_STR
 
 // status word bits
 constexpr uint32_t MERGE_BAD_CODE = 1;   // string code outside its remap

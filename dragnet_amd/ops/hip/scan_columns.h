@@ -81,20 +81,6 @@ __global__ void dict_intern_kernel(StrDict D, const uint8_t* blob,
   code2id[i] = id;
 }
 
-// Ordinal of the file that row r belongs to: the last f with
-// seg_start[f] <= r.  Empty files repeat a value and are never chosen
-// (their successor starts at the same row).  seg_start is a few KB at
-// most, shared by every row: it stays in L2.
-DEV uint32_t file_ordinal(const uint32_t* seg_start, uint32_t nfiles,
-                          uint32_t r) {
-  uint32_t lo = 0, hi = nfiles;  // seg_start[lo] <= r < seg_start[hi]
-  while (hi - lo > 1) {
-    uint32_t mid = lo + ((hi - lo) >> 1);
-    if (seg_start[mid] <= r) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 // Grid-stride over rows.  CODED: string columns are COL_CODED, not
 // COL_STR; the last breakdown of every metric is the reserved file
 // column; an unbucketed string key is code2id's.  X is read only then.

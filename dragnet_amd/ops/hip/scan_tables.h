@@ -1,28 +1,15 @@
-// Concurrent table layer of the scan engine, DEVICE ONLY: relaxed
-// atomics, dictionaries, aggregation insert, the per-block LDS cache.
+// Concurrent table layer of the scan engine, DEVICE ONLY: dictionaries,
+// aggregation insert, the per-block LDS cache.  DEV and the relaxed
+// atomics of the claim-and-publish protocol are dev_util.h's.
 #pragma once
 #include "scan_record.h"
 
 namespace dn {
 
-#define DEV __device__ __forceinline__
-
 constexpr int LDS_CACHE = 128;    // per-block aggregation cache slots
 // (halved from 256 in r2: the 7 KB buys a whole extra block of
 // occupancy, which outweighs extra cache-miss fallthrough; misses
 // go to the dense partial row / global table either way)
-
-template <typename T>
-DEV T atomic_load_relaxed(const T* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <typename T>
-DEV void atomic_store_relaxed(T* p, T v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-DEV void drain_stores() {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
 
 // -------------------------------------------------------------------
 // dictionaries (string + number interning)

@@ -4,6 +4,7 @@
 #pragma once
 #include "common.h"
 #include "dec2dbl.h"
+#include "dev_util.h"  // FNV_OFFSET, mix64
 
 namespace dn {
 
@@ -13,19 +14,12 @@ namespace dn {
 DN_HD_INLINE uint64_t fnv1a_byte(uint64_t h, uint8_t b) {
   return (h ^ (uint64_t)b) * 0x100000001B3ull;
 }
-constexpr uint64_t FNV_OFFSET = 0xCBF29CE484222325ull;
 
 DN_CONST_TABLE double P10_TBL[23] = {
   1e0,1e1,1e2,1e3,1e4,1e5,1e6,1e7,1e8,1e9,1e10,1e11,1e12,1e13,1e14,
   1e15,1e16,1e17,1e18,1e19,1e20,1e21,1e22};
 DN_CONST_TABLE int DIM_TBL[12] = {
   31,28,31,30,31,30,31,31,30,31,30,31};
-
-DN_HD_INLINE uint64_t mix64(uint64_t x) {
-  x ^= x >> 33; x *= 0xFF51AFD7ED558CCDull;
-  x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53ull;
-  x ^= x >> 33; return x;
-}
 
 // -------------------------------------------------------------------
 // byte cursor: 16B-buffered reads from the chunk

@@ -4,7 +4,7 @@
 // multi-GPU gather every rank holds the ranks' string dictionaries as
 // blobs and offsets, and needs one global dictionary ("first seen first,
 // in rank order") and, per rank, the table from its codes to the global
-// ones (dragnet_amd/distributed.py, unify_dictionaries).
+// ones (dragnet_amd/merge.py, unify_dictionaries).
 //
 //   unify_hash_kernel    spans -> one 64-bit hash each; validates spans
 //   unify_insert_kernel  find-or-insert into one open-addressing table

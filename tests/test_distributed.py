@@ -454,7 +454,7 @@ def test_wire_encode_huge_lquantize_ordinal():
     ~1000-bit Python int) must survive the dense wire encode as f64
     keys instead of raising OverflowError (single-process slice of
     the C1 format)."""
-    from dragnet_amd.distributed import _encode_table, _rebuild_table
+    from dragnet_amd.merge import _encode_table, _rebuild_table
     from dragnet_amd.points import Aggregator
     from dragnet_amd.query import query_load
     q = query_load(breakdown_specs="x[aggr=lquantize,step=7]")

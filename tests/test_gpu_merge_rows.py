@@ -179,7 +179,7 @@ def three_aggregators(query, odd_weight):
 def test_reaggregate_gpu_equals_host(odd_weight, monkeypatch):
     """Same keys, values and insertion order as the host path; a
     fractional weight silently takes the host path."""
-    from dragnet_amd.distributed import _encode_table, reaggregate
+    from dragnet_amd.merge import _encode_table, reaggregate
     from dragnet_amd.query import query_load
     q = query_load(breakdown_specs="a,b")
     parts, strings = [], []

@@ -166,8 +166,8 @@ def test_reaggregate_gpu_equals_host(monkeypatch):
     same keys, values and insertion order as the host paths."""
     import torch
 
-    from dragnet_amd.distributed import (_encode_table, _strings_blob,
-                                         reaggregate)
+    from dragnet_amd.merge import (_encode_table, _strings_blob,
+                                   reaggregate)
     from dragnet_amd.points import Aggregator
     from dragnet_amd.query import query_load
     q = query_load(breakdown_specs="a,b")

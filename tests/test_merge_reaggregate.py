@@ -6,8 +6,8 @@ equals _rebuild_table over the parts remapped and concatenated by hand.
 import numpy as np
 import pytest
 
-from dragnet_amd.distributed import (_EL_STR, _encode_table,
-                                     _rebuild_table, reaggregate)
+from dragnet_amd.merge import (_EL_STR, _encode_table, _rebuild_table,
+                               reaggregate)
 from dragnet_amd.points import Aggregator
 from dragnet_amd.query import query_load
 
@@ -52,3 +52,54 @@ def test_reaggregate_host_equals_rebuild(nk, monkeypatch):
     got = reaggregate(q, parts, strings_per_part)
     assert list(got.table.items()) == list(want.table.items())
     assert len(got.table) == len({k[:nk] for t in RANKS for k in t})
+
+
+# (mode, threshold) -> the decision at 0, 9 and 10 items when a GPU is
+# visible; without one every decision is False.  "0" never, "1" always
+# (there is something to do), otherwise from the threshold up, where
+# unset or unparsable is infinity.
+_NEVER, _ALWAYS, _FROM_10 = (False,) * 3, (False, True, True), \
+    (False, False, True)
+POLICY = {
+    (None, None): _NEVER, (None, "abc"): _NEVER, (None, "10"): _FROM_10,
+    ("0", None): _NEVER, ("0", "abc"): _NEVER, ("0", "10"): _NEVER,
+    ("1", None): _ALWAYS, ("1", "abc"): _ALWAYS, ("1", "10"): _ALWAYS,
+    ("auto", None): _NEVER, ("auto", "abc"): _NEVER,
+    ("auto", "10"): _FROM_10,
+}
+
+
+@pytest.mark.parametrize("cuda", [False, True])
+@pytest.mark.parametrize("knobs", ["merge", "unify"])
+def test_path_policy_table(knobs, cuda, monkeypatch):
+    """The one path policy decides for both knob pairs what the two
+    separate functions decided; nk == 0, an empty table and a
+    list-of-str dictionary stay on the host whatever the mode."""
+    import torch
+
+    from dragnet_amd.merge import _merge_on_gpu, _unify_on_gpu
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: cuda)
+    wire = [(np.zeros(4, dtype=np.uint8), np.arange(3, dtype=np.int64))]
+    if knobs == "merge":
+        mode_var, thr_var = "DRAGNET_MERGE_GPU", "DRAGNET_MERGE_GPU_ROWS"
+
+        def decide(count):
+            return _merge_on_gpu(count, 2)
+    else:
+        mode_var, thr_var = "DRAGNET_UNIFY_GPU", "DRAGNET_UNIFY_GPU_STRINGS"
+
+        def decide(count):
+            return _unify_on_gpu(wire, count)
+    for (mode, thr), want in POLICY.items():
+        for var, v in ((mode_var, mode), (thr_var, thr)):
+            if v is None:
+                monkeypatch.delenv(var, raising=False)
+            else:
+                monkeypatch.setenv(var, v)
+        got = tuple(decide(count) for count in (0, 9, 10))
+        assert got == tuple(cuda and w for w in want), (mode, thr)
+        # whatever the mode: a scalar table, strings already on the host
+        assert _merge_on_gpu(10, 0) is False
+        assert _merge_on_gpu(0, 2) is False
+        assert _unify_on_gpu([["a", "b"]], 10) is False
+        assert _unify_on_gpu(wire + [["a"]], 10) is False

@@ -115,7 +115,7 @@ def test_merge_wire_format_roundtrip(items):
     """The dense-merge encoder/decoder round-trips ANY table exactly
     (str/int key elements, int/float values) — the single-rank slice
     of the C1 wire format."""
-    from dragnet_amd.distributed import _encode_table, _rebuild_table
+    from dragnet_amd.merge import _encode_table, _rebuild_table
     from dragnet_amd.points import Aggregator
     from dragnet_amd.query import query_load
     q = query_load(breakdown_specs="a,b")

@@ -1,5 +1,5 @@
 """
-distributed.unify_dictionaries, host path: dictionaries in the wire form
+merge.unify_dictionaries, host path: dictionaries in the wire form
 (blob, offs) give what the decoded lists give, through the seam and
 through reaggregate.
 """
@@ -7,8 +7,8 @@ through reaggregate.
 import numpy as np
 import pytest
 
-from dragnet_amd.distributed import (_encode_table, _strings_blob,
-                                     reaggregate, unify_dictionaries)
+from dragnet_amd.merge import (_encode_table, _strings_blob, reaggregate,
+                               unify_dictionaries)
 from dragnet_amd.points import Aggregator
 from dragnet_amd.query import query_load
 

@@ -1,5 +1,5 @@
 """A/B of the ways to re-aggregate merged tables (the grouping step of
-dragnet_amd.distributed.reaggregate), on one GPU:
+dragnet_amd.merge.reaggregate), on one GPU:
 
     host     np.unique(axis=0) + np.bincount      (DRAGNET_MERGE_GPU=0)
     parent   merge_rows(sort=False), the copy of the g distinct rows and
@@ -40,7 +40,7 @@ import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
-from dragnet_amd import distributed as D  # noqa: E402
+from dragnet_amd import merge as D  # noqa: E402
 
 
 def make_rows(n, nk, groups, seed):
@@ -68,7 +68,7 @@ def device_path(parts, remaps, nk):
 
 
 def parent_device_path(parts, remaps, nk):
-    """distributed._group_rows_device before merge_rows had sort=."""
+    """merge._group_rows_device before merge_rows had sort=."""
     import torch
 
     from dragnet_amd.ops import load_ops

@@ -1,5 +1,5 @@
 """A/B of the two ways to build the global string dictionary and the
-per-rank remap tables (dragnet_amd.distributed.unify_dictionaries), on
+per-rank remap tables (dragnet_amd.merge.unify_dictionaries), on
 one GPU:
 
     host     blob D2H + _decode_strings + the dict loop (DRAGNET_UNIFY_GPU=0)
@@ -36,7 +36,7 @@ import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
-from dragnet_amd import distributed as D  # noqa: E402
+from dragnet_amd import merge as D  # noqa: E402
 
 WORLD = 8
 ALPHABET = np.frombuffer(

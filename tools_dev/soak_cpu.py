@@ -144,7 +144,7 @@ def soak_pipeline():
 
 
 def soak_wire():
-    from dragnet_amd.distributed import _encode_table, _rebuild_table
+    from dragnet_amd.merge import _encode_table, _rebuild_table
     from dragnet_amd.points import Aggregator
     from dragnet_amd.query import query_load
     bad = 0
