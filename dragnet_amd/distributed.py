@@ -38,8 +38,8 @@ import numpy as np
 
 # _rebuild_table: not called here, importable beside _encode_table, its inverse
 from .merge import (_EL_STR, _encode_table, _group_rows, _np,  # noqa: F401
-                    _rebuild_table, _strings_blob, reaggregate,
-                    unify_dictionaries)
+                    _rebuild_table, _strings_blob, partition_rows,
+                    reaggregate, unify_dictionaries)
 
 _PARTITION_ROWS = 1 << 20  # switch to hash-partition all_to_all above
 
@@ -196,27 +196,17 @@ def _merge_partitioned(query, codes, tagpack, vals, dicts, device, group):
 
     # C2 first: unify dictionaries globally
     gstrings, remaps = unify_dictionaries(dicts, device)
-    my_remap = _np(remaps[rank])
-    for j in range(nk):
-        is_str = ((tagpack >> (2 * j)) & 3) == _EL_STR
-        if is_str.any():
-            codes[is_str, j] = my_remap[codes[is_str, j]]
 
-    # partition rows by key hash
-    h = np.zeros(codes.shape[0], dtype=np.uint64)
-    for j in range(nk):
-        cj = np.ascontiguousarray(codes[:, j]).view(np.uint64)
-        h = (h ^ cj) * np.uint64(0x100000001B3)
-    h ^= tagpack.view(np.uint64)
-    part = (h % np.uint64(world)).astype(np.int64)
-    order = np.argsort(part, kind="stable")
-    counts = np.bincount(part, minlength=world)
-
-    row = np.concatenate(
-        [codes, tagpack[:, None], vals.view(np.int64)[:, None]],
-        axis=1)[order]  # [n, nk+2] i64 rows, grouped by target rank
-    send = _to_device(row.reshape(-1), torch.int64, device)
-    in_counts = torch.from_numpy(counts * (nk + 2)).to(device)
+    # remap, hash each row to its rank, group by rank (merge.py: host or
+    # GPU, same bits); remaps[rank] goes in where the unify left it
+    wire, counts = partition_rows(codes, tagpack, vals, remaps[rank], world,
+                                  device)
+    if torch.is_tensor(wire):
+        send = wire.reshape(-1).to(device)
+        in_counts = (counts * (nk + 2)).to(device)
+    else:
+        send = _to_device(wire.reshape(-1), torch.int64, device)
+        in_counts = torch.from_numpy(counts * (nk + 2)).to(device)
     out_counts = torch.empty_like(in_counts)
     dist.all_to_all_single(out_counts, in_counts, group=group)
     recv = torch.empty(int(out_counts.sum().item()), dtype=torch.int64,

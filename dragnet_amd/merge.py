@@ -14,8 +14,12 @@ and hands the gathered tensors to reaggregate().
   C1 _group_rows: remap the string codes, group identical rows and sum
      their values: np.unique + bincount on the host, or the merge_rows
      kernels (ops/hip/merge_rows.h, ordered by sort_rows.h).
-  DRAGNET_UNIFY_GPU and DRAGNET_MERGE_GPU choose (_use_gpu); the host
-  and device paths give the same bits.
+  partition_rows: the high-cardinality merge sends each row to the rank
+     its hash names; remap, hash and a stable split by destination:
+     numpy on the host, or the partition_rows kernels
+     (ops/hip/partition_rows.h) with the remap table where unify left it.
+  DRAGNET_UNIFY_GPU, DRAGNET_MERGE_GPU and DRAGNET_PARTITION_GPU choose
+  (_use_gpu); the host and device paths give the same bits.
 """
 
 import os
@@ -139,7 +143,7 @@ def _rebuild_table(query, codes, tagpack, vals, strings):
 # ---- what the host and device paths share ------------------------------
 
 def _use_gpu(mode_var, threshold_var, count):
-    """The path policy of both device steps.  Mode "0": never the GPU;
+    """The path policy of the device steps.  Mode "0": never the GPU;
     "1": whenever one is visible; anything else ("auto", the default):
     from `threshold_var` items up, where unset or unparsable means
     infinity: auto then never selects it.  No items: the host."""
@@ -370,6 +374,77 @@ def unify_dictionaries(dicts, device=None):
     if _unify_on_gpu(dicts, n_strings):
         return _unify_device(dicts, device)
     return _unify_host(dicts)
+
+
+# ---- partition by destination rank ---------------------------------------
+
+_PARTITION_MAX_WORLD = 256  # ops/hip/partition_rows.h: a thread per bin
+
+
+def _partition_host(codes, tagpack, vals, remap, world):
+    """Remap, hash, stable argsort by hash % world: the reference the
+    device path must equal bit for bit."""
+    tagpack = _np(tagpack).astype(np.int64, copy=False)
+    codes = _np(codes).astype(np.int64, copy=True)  # the caller's stay
+    vals = _np(vals).astype(np.float64, copy=False)
+    nk = codes.shape[1]
+    if remap is not None:
+        remap = _np(remap)  # a device slice after a GPU unify
+        for j in range(nk):
+            is_str = ((tagpack >> (2 * j)) & 3) == _EL_STR
+            if is_str.any():
+                codes[is_str, j] = remap[codes[is_str, j]]
+    h = np.zeros(codes.shape[0], dtype=np.uint64)
+    for j in range(nk):
+        cj = np.ascontiguousarray(codes[:, j]).view(np.uint64)
+        h = (h ^ cj) * np.uint64(0x100000001B3)
+    h ^= tagpack.view(np.uint64)
+    part = (h % np.uint64(world)).astype(np.int64)
+    order = np.argsort(part, kind="stable")
+    counts = np.bincount(part, minlength=world)
+    wire = np.concatenate(
+        [codes, tagpack[:, None], vals.view(np.int64)[:, None]],
+        axis=1)[order]
+    return wire, counts
+
+
+def _partition_device(codes, tagpack, vals, remap, world, device):
+    """One partition_rows call; the remap table is used where it lies
+    and the wire rows and counts stay on the device."""
+    import torch
+
+    from .ops import load_ops
+    ops = load_ops(required=True)  # a missing extension is an error
+    device, up = _work_device(device, [codes, remap])
+    rows = torch.cat([up(codes, torch.int64),
+                      up(tagpack, torch.int64).reshape(-1, 1)], dim=1)
+    return ops.partition_rows(
+        rows, up(vals, torch.float64), rows.shape[1] - 1, world,
+        remap=None if remap is None else up(remap, torch.int64))
+
+
+def partition_rows(codes, tagpack, vals, remap, world, device=None):
+    """Split one rank's table by the rank that will merge each row.
+    codes [n, nk], tagpack [n] and vals [n] are numpy or torch on any
+    device; remap is the int64 table of this rank's string-tagged codes
+    (unify_dictionaries), numpy or a device tensor, or None.  Row i,
+    after the remap, goes to rank hash(row i) % world.  Returns (wire
+    int64 [n, nk + 2], counts int64 [world]): the remapped codes, the
+    tag pack and the bits of the value of every row, grouped by
+    destination in rank order, input order kept within a group, and
+    the rows per destination.
+
+    The host path (numpy arrays out) is the stable argsort; the device
+    path (tensors on the GPU out) is the partition_rows kernels.
+    DRAGNET_PARTITION_GPU and DRAGNET_PARTITION_GPU_ROWS choose
+    (_use_gpu; infinity by default: profiles/r12_partition_rows.md);
+    more than 256 ranks, or a table without breakdowns, stay on the
+    host.  Both give the same bits."""
+    n, nk = codes.shape
+    if nk >= 1 and world <= _PARTITION_MAX_WORLD and _use_gpu(
+            "DRAGNET_PARTITION_GPU", "DRAGNET_PARTITION_GPU_ROWS", n):
+        return _partition_device(codes, tagpack, vals, remap, world, device)
+    return _partition_host(codes, tagpack, vals, remap, world)
 
 
 def reaggregate(query, parts, strings_per_part, device=None):

@@ -110,7 +110,8 @@ ScanKernel xpose_kernel(int mw, int xg) {
 }  // namespace
 }  // namespace dn
 
-#include "ext_merge.h"  // sort_rows, merge_rows, unify_strings
+// sort_rows, merge_rows, unify_strings, partition_rows
+#include "ext_merge.h"
 
 namespace dn {
 
@@ -733,6 +734,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("max_blocks") = 0,
         "number the distinct byte strings among spans of a GPU blob in "
         "order of first occurrence -> (remap int64 [n], first int64 [g])");
+  m.def("partition_rows", &dn::partition_rows, py::arg("rows"),
+        py::arg("vals"), py::arg("nk"), py::arg("world"),
+        py::arg("remap") = py::none(), py::arg("max_blocks") = 0,
+        "remap, hash and split int64 rows by hash % world, stably -> "
+        "(wire [n, nk + 2] grouped by bin, counts int64 [world])");
   m.def("lds_bytes", &dn::lds_bytes, py::arg("nf"), py::arg("nm"),
         py::arg("ns") = 0, py::arg("columnar") = false,
         "dynamic LDS bytes of a scan / columnar launch (host only)");

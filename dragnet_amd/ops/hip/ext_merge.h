@@ -1,8 +1,9 @@
 // Host bindings of the merge layer, the step after the multi-GPU gather
 // (dragnet_amd/merge.py): sort_rows (sort_rows.h), merge_rows
-// (merge_rows.h) and unify_strings (unify_strings.h), free functions
-// that keep nothing between calls.  Part of ext.hip's translation unit,
-// behind its launch plumbing (launch, on_dev, allocating, GRID_CAP).
+// (merge_rows.h), unify_strings (unify_strings.h) and partition_rows
+// (partition_rows.h), free functions that keep nothing between calls.
+// Part of ext.hip's translation unit, behind its launch plumbing (launch,
+// on_dev, allocating, GRID_CAP).
 #pragma once
 
 namespace dn {
@@ -374,6 +375,93 @@ std::tuple<torch::Tensor, torch::Tensor> unify_strings(
               "start or length, or an end beyond ", blob.numel(), " bytes)");
   TORCH_CHECK(!(status & UNIFY_FULL), "unify_strings: unify table full");
   return std::make_tuple(remap, first.narrow(0, 0, g));
+}
+
+// Split rows by destination rank (partition_rows.h): rows is int64 [n,
+// nk + 1] (key codes, then the tag pack), vals f64 [n], remap the int64
+// table of the string-tagged codes (none: the codes pass through).  Row
+// i goes to bin hash(row i) % world, world in 1..PART_MAX_WORLD.  Returns
+// wire int64 [n, nk + 2] (remapped codes, tag pack, bits of the value),
+// grouped by bin, input order kept within a bin, and counts int64
+// [world] on the device.  max_blocks > 0 caps the grids (tests).  n == 0
+// launches nothing.  Syncs once, to read the status word.
+std::tuple<torch::Tensor, torch::Tensor> partition_rows(
+    torch::Tensor rows, torch::Tensor vals, int64_t nk, int64_t world,
+    c10::optional<torch::Tensor> remap, int64_t max_blocks) {
+  const auto dev = rows.device();
+  TORCH_CHECK(nk >= 1 && nk <= MAX_KEY, "partition_rows: nk must be 1..",
+              (int)MAX_KEY);
+  TORCH_CHECK(world >= 1 && world <= PART_MAX_WORLD,
+              "partition_rows: world must be 1..", (int)PART_MAX_WORLD,
+              ", got ", world);
+  const int64_t w = nk + 1;
+  check_arg("partition_rows", "rows", rows, torch::kInt64, 2, dev);
+  TORCH_CHECK(rows.size(1) == w, "partition_rows: rows must be [n, nk + 1]");
+  const int64_t n = rows.size(0);
+  check_arg("partition_rows", "vals", vals, torch::kFloat64, 1, dev);
+  TORCH_CHECK(vals.size(0) == n, "partition_rows: rows has ", n,
+              " rows, vals has ", vals.size(0));
+  TORCH_CHECK(n < ((int64_t)1 << 31), "partition_rows: n exceeds 2^31 rows");
+  TORCH_CHECK(max_blocks >= 0, "partition_rows: max_blocks is negative");
+  if (remap.has_value())
+    check_arg("partition_rows", "remap", *remap, torch::kInt64, 1, dev);
+  const auto i32 = on_dev(dev, torch::kInt32);
+  const auto i64 = on_dev(dev, torch::kInt64);
+  if (n == 0)
+    return std::make_tuple(torch::empty({0, w + 1}, i64),
+                           torch::zeros({world}, i64));
+
+  c10::DeviceGuard guard(dev);
+  // a round is loaded 16 bytes at a time from the base of rows
+  if ((uintptr_t)rows.data_ptr() % 16 != 0) rows = rows.clone();
+
+  const int64_t ntiles = (n + SORT_TILE - 1) / SORT_TILE;
+  const int64_t total = world * ntiles;  // <= 2^8 * 2^20
+  const int64_t total8 = (total + 7) / 8 * 8;
+  const int64_t nsums = (total8 + SORT_SCAN_TILE - 1) / SORT_SCAN_TILE;
+  torch::Tensor wire, counts, hist, sums, status;
+  allocating([&] {
+    wire = torch::empty({n, w + 1}, i64);
+    counts = torch::empty({world}, i64);
+    hist = torch::empty({total8}, i32);
+    sums = torch::empty({nsums}, i32);
+    status = torch::zeros({1}, i32);
+  }, "cannot allocate the partition buffers (", n, " wire rows of ", w + 1,
+     " words and ", total8, " counts)");
+  PartArgs A = {};
+  A.rows = (const long long*)rows.data_ptr();
+  A.remapped = remap.has_value();
+  if (A.remapped) {
+    A.remap = (const long long*)remap->data_ptr();
+    A.m = remap->numel();
+  }
+  A.n = (uint32_t)n;
+  A.nk = (int)nk;
+  A.world = (uint32_t)world;
+  while ((1u << A.nbits) < A.world) A.nbits++;
+  A.c32 = (uint32_t)(((uint64_t)1 << 32) % (uint64_t)world);
+
+  int64_t blocks = ntiles;
+  if (max_blocks > 0) blocks = std::min(blocks, max_blocks);
+  uint32_t* hp = (uint32_t*)hist.data_ptr();
+  uint32_t* sp = (uint32_t*)sums.data_ptr();
+  launch("partition_hist", partition_hist_kernel, dim3((uint32_t)blocks),
+         dim3(SORT_BLOCK), 0, A, hp, (uint32_t)ntiles,
+         (uint32_t)(total8 - total), (uint32_t*)status.data_ptr());
+  launch("sort_scan", sort_scan_kernel, dim3((uint32_t)nsums),
+         dim3(SORT_BLOCK), 0, hp, (uint32_t)total8, sp);
+  launch("sort_scan_sums", sort_scan_sums_kernel, dim3(1), dim3(SORT_BLOCK),
+         0, sp, (uint32_t)nsums);
+  launch("partition_scatter", partition_scatter_kernel,
+         dim3((uint32_t)blocks), dim3(SORT_BLOCK), 0, A,
+         (const long long*)vals.data_ptr(), (const uint32_t*)hp,
+         (const uint32_t*)sp, (uint32_t)ntiles,
+         (long long*)wire.data_ptr(), (long long*)counts.data_ptr());
+  const uint32_t bits = (uint32_t)status.cpu().data_ptr<int32_t>()[0];
+  TORCH_CHECK(!(bits & PART_BAD_CODE),
+              "partition_rows: a string-tagged code lies outside the remap "
+              "table of ", A.m, " entries");
+  return std::make_tuple(wire, counts);
 }
 
 }  // namespace dn

@@ -21,7 +21,8 @@
 // scan_columns.h (device only: the index queries over typed columns),
 // merge_rows.h (device only: re-aggregation of merged multi-GPU tables),
 // sort_rows.h (device only: radix sort of the merged rows),
-// unify_strings.h (device only: one dictionary out of the ranks').
+// unify_strings.h (device only: one dictionary out of the ranks'),
+// partition_rows.h (device only: the rows of a rank split by destination).
 
 #include "common.h"
 #include <hip/hip_runtime.h>
@@ -605,5 +606,8 @@ __global__ void extract_numdict_kernel(NumDict D, double* out_vals,
 
 // first-occurrence numbering of the ranks' dictionary strings; last again
 #include "unify_strings.h"
+
+// stable split of a rank's rows by the rank that merges them; last again
+#include "partition_rows.h"
 
 }  // extern "C++"
