@@ -69,15 +69,20 @@ class ScanResult(object):
     gpu_stats (GPU engine scans; empty otherwise) tells how the scan
     coped with its table sizes: "restarts" (whole-scan reruns), and
     in-place growths per structure — "agg" (a list, per metric),
-    "sdict", "sdata", "ndict"."""
+    "sdict", "sdata", "ndict".
+
+    wire_tables (empty unless a distributed scan asked the GPU engine
+    for them and DRAGNET_ENCODE_GPU chose the device): one
+    merge.WireTable per query, in place of the aggregators."""
 
     def __init__(self, aggregators, stages, files=None, nonroot=False,
-                 gpu_stats=None):
+                 gpu_stats=None, wire_tables=None):
         self.aggregators = aggregators
         self.stages = stages
         self.files = files or []
         self.nonroot = nonroot
         self.gpu_stats = gpu_stats or {}
+        self.wire_tables = wire_tables or []
 
 
 class FileDatasource(object):

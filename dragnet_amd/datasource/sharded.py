@@ -31,11 +31,23 @@ def _patch_agg_stage(stages, merged_aggs):
     return out
 
 
+def _local_tables(result):
+    """What this rank hands to the merge: the scan's wire tables where
+    it left them on the device, else its aggregators."""
+    return getattr(result, "wire_tables", None) or result.aggregators
+
+
 class ShardedDatasource(FileDatasource):
     def __init__(self, ds, engine=None):
         super().__init__(ds, engine=engine)
         self.rank, self.world, self.local_rank = dist_env()
         self.dist = init_process_group() if self.world > 1 else None
+
+    def _scan_kw(self):
+        """Ask the GPU engine of a multi-rank scan for wire tables."""
+        if self.world > 1 and getattr(self.engine(), "name", "") == "gpu":
+            return {"wire": True}
+        return {}
 
     def _shard(self, files):
         if self.world <= 1:
@@ -60,11 +72,11 @@ class ShardedDatasource(FileDatasource):
             files=mine, queries=[query],
             ds_filter=self.ds.filter,
             time_field=self.ds.time_field,
-            data_format=self.ds.data_format)
+            data_format=self.ds.data_format, **self._scan_kw())
         if self.world <= 1:
             result.stages = counters.stages() + result.stages
             return result
-        merged = merge_aggregators(result.aggregators, [query])
+        merged = merge_aggregators(_local_tables(result), [query])
         stages = _patch_agg_stage(
             merge_counter_stages(result.stages), merged)
         if self.rank != 0:
@@ -94,11 +106,11 @@ class ShardedDatasource(FileDatasource):
             files=mine, queries=queries,
             ds_filter=self.ds.filter,
             time_field=self.ds.time_field,
-            data_format=self.ds.data_format)
+            data_format=self.ds.data_format, **self._scan_kw())
         if self.world <= 1:
             result.stages = counters.stages() + result.stages
             return result
-        merged = merge_aggregators(result.aggregators, queries)
+        merged = merge_aggregators(_local_tables(result), queries)
         stages = _patch_agg_stage(
             merge_counter_stages(result.stages), merged)
         if self.rank != 0:

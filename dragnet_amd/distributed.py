@@ -37,9 +37,10 @@ import os
 import numpy as np
 
 # _rebuild_table: not called here, importable beside _encode_table, its inverse
-from .merge import (_EL_STR, _encode_table, _group_rows, _np,  # noqa: F401
-                    _rebuild_table, _strings_blob, partition_rows,
-                    reaggregate, unify_dictionaries)
+from .merge import (_EL_STR, WireTable, _encode_table,  # noqa: F401
+                    _group_rows, _np, _rebuild_table, _strings_blob,
+                    encode_table, partition_rows, reaggregate,
+                    unify_dictionaries)
 
 _PARTITION_ROWS = 1 << 20  # switch to hash-partition all_to_all above
 
@@ -109,6 +110,8 @@ def _all_gather_padded(t, sizes, device, group):
 
 def _to_device(arr, dtype, device):
     import torch
+    if torch.is_tensor(arr):  # a device wire table: no upload
+        return arr.contiguous().to(device=device, dtype=dtype)
     return torch.from_numpy(np.ascontiguousarray(arr)).to(
         device=device, dtype=dtype)
 
@@ -119,27 +122,31 @@ def _gather_dictionaries(blob, soffs, ns_strs, ns_blob, device, group):
     import torch
     g_soffs = _all_gather_padded(_to_device(soffs, torch.int64, device),
                                  list(ns_strs + 1), device, group)
-    g_blob = _all_gather_padded(
-        _to_device(np.frombuffer(blob, dtype=np.uint8).copy(), torch.uint8,
-                   device), list(ns_blob), device, group)
+    g_blob = _all_gather_padded(_to_device(blob, torch.uint8, device),
+                                list(ns_blob), device, group)
     return list(zip(g_blob, g_soffs))
 
 
 def merge_tables_tensor(agg, query, device=None, group=None):
     """Dense RCCL merge of one aggregation table (C1+C2); every rank
     returns the fully-merged Aggregator (allreduce semantics).  See
-    module docstring for the wire format; no object serialization."""
+    module docstring for the wire format; no object serialization.
+    agg is this rank's Aggregator, encoded here on the host, or its
+    WireTable (merge.encode_table): one on the device is neither
+    encoded nor uploaded."""
     import torch
     import torch.distributed as dist
 
     if device is None:
         device = _coll_device(group)
     nk = len(query.breakdowns)
-    codes, tagpack, vals, strings = _encode_table(agg, nk)
-    blob, soffs = _strings_blob(strings)
+    if not isinstance(agg, WireTable):
+        agg = encode_table(agg, query)
+    codes, tagpack, vals = agg.codes, agg.tagpack, agg.vals
+    blob, soffs = agg.strings
 
     world = dist.get_world_size(group)
-    meta = torch.tensor([codes.shape[0], len(strings), len(blob)],
+    meta = torch.tensor([codes.shape[0], len(soffs) - 1, len(blob)],
                         dtype=torch.int64, device=device)
     metas = [torch.empty(3, dtype=torch.int64, device=device)
              for _ in range(world)]

@@ -90,7 +90,11 @@ class GpuEngine(object):
     # ---- public engine interface ----
 
     def scan(self, files, queries, ds_filter=None, time_field=None,
-             data_format="json", byte_source=None):
+             data_format="json", byte_source=None, wire=False):
+        """wire: the caller merges across ranks and takes the tables in
+        wire form where the policy says device (merge.encode_on_gpu):
+        the result then carries wire_tables, one per query, and no
+        aggregators."""
         from ..datasource.file import ScanResult
 
         cplan = planmod.compile_plan(
@@ -118,9 +122,9 @@ class GpuEngine(object):
                 # partial aggregate
                 raise RuntimeError(
                     "table overflow on non-restartable byte source")
-            aggs, stages = ctx.finalize(queries)
+            aggs, stages, wires = ctx.finalize_wire(queries, wire)
             return ScanResult(aggs, stages, gpu_stats=dict(
-                ctx.planner.grow_counts(), restarts=0))
+                ctx.planner.grow_counts(), restarts=0), wire_tables=wires)
 
         dense = None
         nogrow = {"agg": [0] * len(queries), "sdict": 0, "sdata": 0,
@@ -147,9 +151,10 @@ class GpuEngine(object):
                 dict_slots *= 8
                 dict_data *= 4
                 continue
-            aggs, stages = ctx.finalize(queries)
+            aggs, stages, wires = ctx.finalize_wire(queries, wire)
             return ScanResult(aggs, stages,
-                              gpu_stats=dict(nogrow, restarts=attempt))
+                              gpu_stats=dict(nogrow, restarts=attempt),
+                              wire_tables=wires)
         raise RuntimeError("aggregation tables overflowed after retries")
 
     def columnar_query(self, query, filt, params, kinds, cols, vals):
@@ -651,6 +656,49 @@ class _ScanContext(object):
     def finalize(self, queries):
         return self.decode_extracted(self.extract_async(queries),
                                      queries)
+
+    def finalize_wire(self, queries, wire=True):
+        """-> (aggregators, stages, wire tables).  With wire, and where
+        extract_wire serves every query, the tables stay on the device
+        in wire form and there are no aggregators; otherwise the
+        snapshot is decoded on the host and there are no wire tables."""
+        h = self.extract_async(queries)
+        wires = self.extract_wire(queries, h) if wire else None
+        if wires is None:
+            return self.decode_extracted(h, queries) + ([],)
+        stages = decode.counter_stages(h["cnt"].cpu().numpy(), self.cplan,
+                                       queries)
+        for name, c in stages:
+            if name == "Aggregator":  # this rank's; the merge patches it
+                c["noutputs"] = int(wires[0].vals.shape[0])
+        return [], stages, wires
+
+    def extract_wire(self, queries, h=None):
+        """The extraction (extract_async's handle, or a fresh one) to
+        one merge.WireTable per query, on the device: the encode_table
+        kernels (ops/hip/encode_table.h) per metric, no row becoming a
+        Python object.  None where any query is not served: one without
+        breakdowns, a table below DRAGNET_ENCODE_GPU's threshold
+        (merge.encode_on_gpu), or a refusal of the kernels; the caller
+        then decodes the same handle on the host."""
+        from .. import merge
+        if h is None:
+            h = self.extract_async(queries)
+        h["ev"].synchronize()
+        cnt = h["cnt"].cpu().numpy()
+        wires = []
+        for m, q in enumerate(queries):
+            n = min(int(h["aggs"][m][2].item()), h["aggs"][m][0].shape[0])
+            if not merge.encode_on_gpu(n, len(q.breakdowns)):
+                return None
+            w = merge.encode_table(h, q, metric=m)
+            if w is None:
+                return None
+            mc = cnt[C_GLOBAL_N + m * CM_N:C_GLOBAL_N + (m + 1) * CM_N]
+            w.ninputs = int(mc[CM_AGG_IN])
+            w.ndropped_nonnumeric = int(mc[CM_NONNUMERIC])
+            wires.append(w)
+        return wires
 
     def extract_async(self, queries):
         """Enqueue the table/dictionary extraction kernels and snapshot

@@ -463,10 +463,27 @@ SPECIAL_ARRJSON = 6  # | (string-dict id << 3)
 EMPTY_CODE = 0xFFFFFFFF
 
 
+def number_key(num):
+    """The key string of a number in a plain column: JS String(number)."""
+    from ..points import js_num_str
+    return js_num_str(int(num) if float(num).is_integer()
+                      and abs(num) < 2**53 else float(num))
+
+
+def array_key(raw):
+    """The key string of an array from its JSON text: JS
+    Array.toString, or the text itself where it does not parse."""
+    import json as _json
+    from ..points import js_array_str
+    try:
+        return js_array_str(_json.loads(raw))
+    except ValueError:
+        return raw
+
+
 def decode_key(codes, query, strings, numbers):
     """Decode one metric key tuple (list of u32 codes) into the CPU
     aggregator's canonical key tuple."""
-    from ..points import js_num_str
     out = []
     for b, code in zip(query.breakdowns, codes):
         tag = code >> 30
@@ -485,18 +502,10 @@ def decode_key(codes, query, strings, numbers):
             if "date" in b:
                 out.append(int(num))
             else:
-                out.append(js_num_str(
-                    int(num) if float(num).is_integer()
-                    and abs(num) < 2**53 else float(num)))
+                out.append(number_key(num))
         elif tag == TAG_SPECIAL:
             if (val & 7) == SPECIAL_ARRJSON:
-                import json as _json
-                from ..points import js_array_str
-                raw = strings[val >> 3]
-                try:
-                    out.append(js_array_str(_json.loads(raw)))
-                except ValueError:
-                    out.append(raw)
+                out.append(array_key(strings[val >> 3]))
             else:
                 out.append({
                     SPECIAL_NULL: "null", SPECIAL_UNDEF: "undefined",

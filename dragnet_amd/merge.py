@@ -6,7 +6,15 @@ and hands the gathered tensors to reaggregate().
   wire form: a rank's table is an int64 key-code matrix [n, nk], a tag
      column (2 bits per element: int / string-id / f64-bits) and an f64
      value vector (_encode_table); its string dictionary is a UTF-8 byte
-     blob + offset array (_strings_blob).
+     blob + offset array (_strings_blob).  The dictionary may name one
+     string twice (two scan ids of one string, the constant null beside
+     a literal "null", "a" beside "\\u0061") and the table may hold one
+     key in two rows: every consumer unifies the dictionaries and
+     regroups the rows first (reaggregate, _merge_partitioned).
+  encode_table: an Aggregator to that form row by row on the host, or a
+     scan's extraction snapshot to it on the device, where it lies: the
+     encode_table kernels (ops/hip/encode_table.h); a WireTable either
+     way.  DRAGNET_ENCODE_GPU chooses (encode_on_gpu).
   C2 unify_dictionaries: the global dictionary, first seen first in rank
      order, and per rank the table from its codes to global ones:
      FirstSeen on the host, or the unify_strings kernels
@@ -82,6 +90,105 @@ def _strings_blob(strings):
     if bs:
         np.cumsum([len(b) for b in bs], out=offs[1:])
     return b"".join(bs), offs
+
+
+class WireTable(object):
+    """One rank's table of one query in wire form: codes [n, nk],
+    tagpack [n], vals [n] and the dictionary (blob, offs), numpy or
+    torch on any device, with the scan's ninputs and
+    ndropped_nonnumeric for that query."""
+
+    __slots__ = ("codes", "tagpack", "vals", "strings", "ninputs",
+                 "ndropped_nonnumeric")
+
+    def __init__(self, codes, tagpack, vals, strings, ninputs=0,
+                 ndropped_nonnumeric=0):
+        self.codes, self.tagpack, self.vals = codes, tagpack, vals
+        self.strings = strings
+        self.ninputs = ninputs
+        self.ndropped_nonnumeric = ndropped_nonnumeric
+
+
+def col_kinds(query):
+    """Per breakdown, what ops/hip/encode_table.h needs of it: 2 for a
+    bucketized column, 1 for a date column without bucketizer, else 0."""
+    return [2 if query.bucketizers.get(b["name"]) is not None
+            else 1 if "date" in b else 0 for b in query.breakdowns]
+
+
+def encode_on_gpu(n_rows, nk):
+    """Path choice of the wire-form export: _use_gpu over
+    DRAGNET_ENCODE_GPU and DRAGNET_ENCODE_GPU_ROWS rows of one table
+    (infinity by default: profiles/r13_encode_table.md).  A table
+    without breakdowns is a scalar and stays on the host."""
+    return nk >= 1 and _use_gpu("DRAGNET_ENCODE_GPU",
+                                "DRAGNET_ENCODE_GPU_ROWS", n_rows)
+
+
+def _encode_device(snap, metric, query):
+    """The encode_table kernels (ops/hip/encode_table.h) on metric
+    `metric` of an extraction snapshot (ScanState.extract_all's dict of
+    device tensors): (codes, tagpack, vals, (blob, offs)) on the
+    device, row i being extraction row i, or None where the kernels
+    refuse (NaN or an infinity in an integer column: the host path
+    raises there).  The device renders plain strings, integral numbers
+    and the constants; the E exceptions it hands back (escaped or
+    ill-formed strings, array texts, other numbers) are rendered here,
+    once per distinct value, by the host path's own functions, and
+    appended to the dictionary in the order their codes assume."""
+    import torch
+
+    from .engine.decode import decode_json_string
+    from .engine.plan import array_key, number_key
+    from .ops import load_ops
+    ops = load_ops(required=True)  # a missing extension is an error
+    keys, counts, n = snap["aggs"][metric]
+    (codes, tagpack, vals, blob, offs, exc_kind, _exc_id, exc_blob,
+     exc_offs, refused) = ops.encode_table(
+        keys, counts, n, snap["str_off"], snap["str_len"], snap["n_str"],
+        snap["blob"], snap["used"], snap["numbers"], snap["n_num"],
+        col_kinds(query))
+    if refused:
+        return None
+    if exc_kind.numel():
+        raw = exc_blob.cpu().numpy().tobytes()
+        at = exc_offs.cpu().tolist()
+        extra = []
+        for kind, a, b in zip(exc_kind.cpu().tolist(), at, at[1:]):
+            if kind == 2:
+                s = number_key(np.frombuffer(raw[a:b], np.float64)[0])
+            else:
+                s = decode_json_string(raw[a:b])
+                if kind == 1:
+                    s = array_key(s)
+            extra.append(s.encode("utf-8"))
+        ends = np.cumsum([len(e) for e in extra]).astype(np.int64)
+        blob = torch.cat([blob, torch.from_numpy(np.frombuffer(
+            b"".join(extra), dtype=np.uint8).copy()).to(blob.device)])
+        offs = torch.cat([offs,
+                          offs[-1] + torch.from_numpy(ends).to(offs.device)])
+    return codes, tagpack, vals, (blob, offs)
+
+
+def encode_table(source, query, metric=0):
+    """A table to the wire form, a WireTable.  An Aggregator goes
+    through the host form, _encode_table and _strings_blob (numpy
+    out).  An extraction snapshot (ScanState.extract_all's dict) goes
+    through the encode_table kernels for its metric `metric` (device
+    tensors out) and never becomes Python objects; None where the
+    kernels refuse, and the caller decodes the snapshot on the host.
+    Callers choose by encode_on_gpu.  Both describe the same table: the
+    device form keeps the extraction's rows and may name one string
+    twice, which every consumer unifies and regroups."""
+    nk = len(query.breakdowns)
+    if isinstance(source, Aggregator):
+        codes, tagpack, vals, strings = _encode_table(source, nk)
+        blob, offs = _strings_blob(strings)
+        return WireTable(codes, tagpack, vals,
+                         (np.frombuffer(blob, dtype=np.uint8).copy(), offs),
+                         source.ninputs, source.ndropped_nonnumeric)
+    out = _encode_device(source, metric, query)
+    return None if out is None else WireTable(*out)
 
 
 def _decode_strings(blob_bytes, offs):

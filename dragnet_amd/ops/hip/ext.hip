@@ -110,7 +110,7 @@ ScanKernel xpose_kernel(int mw, int xg) {
 }  // namespace
 }  // namespace dn
 
-// sort_rows, merge_rows, unify_strings, partition_rows
+// sort_rows, merge_rows, unify_strings, partition_rows, encode_table
 #include "ext_merge.h"
 
 namespace dn {
@@ -739,6 +739,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("remap") = py::none(), py::arg("max_blocks") = 0,
         "remap, hash and split int64 rows by hash % world, stably -> "
         "(wire [n, nk + 2] grouped by bin, counts int64 [world])");
+  m.def("encode_table", &dn::encode_table, py::arg("keys"),
+        py::arg("counts"), py::arg("n"), py::arg("str_off"),
+        py::arg("str_len"), py::arg("n_str"), py::arg("blob"),
+        py::arg("used"), py::arg("numbers"), py::arg("n_num"),
+        py::arg("col_kind"),
+        "one metric of a scan's extraction to the wire form -> (codes, "
+        "tagpack, vals, dict_blob, dict_offs, exc_kind, exc_id, exc_blob, "
+        "exc_offs, refused)");
   m.def("lds_bytes", &dn::lds_bytes, py::arg("nf"), py::arg("nm"),
         py::arg("ns") = 0, py::arg("columnar") = false,
         "dynamic LDS bytes of a scan / columnar launch (host only)");
@@ -778,5 +786,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("SORT_TILE") = (int)dn::SORT_TILE;
   m.attr("UNIFY_TILE") = (int)dn::UNIFY_TILE;
   m.attr("UNIFY_STAGE_BYTES") = (int)dn::UNIFY_STAGE_BYTES;
+  m.attr("ENC_STAGE_BYTES") = (int)dn::ENC_STAGE_BYTES;
   m.attr("MAX_FIELDS") = (int)dn::MAX_FIELDS;
 }

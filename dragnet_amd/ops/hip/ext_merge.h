@@ -1,7 +1,8 @@
 // Host bindings of the merge layer, the step after the multi-GPU gather
 // (dragnet_amd/merge.py): sort_rows (sort_rows.h), merge_rows
-// (merge_rows.h), unify_strings (unify_strings.h) and partition_rows
-// (partition_rows.h), free functions that keep nothing between calls.
+// (merge_rows.h), unify_strings (unify_strings.h), partition_rows
+// (partition_rows.h) and encode_table (encode_table.h), free functions
+// that keep nothing between calls.
 // Part of ext.hip's translation unit, behind its launch plumbing (launch,
 // on_dev, allocating, GRID_CAP).
 #pragma once
@@ -462,6 +463,182 @@ std::tuple<torch::Tensor, torch::Tensor> partition_rows(
               "partition_rows: a string-tagged code lies outside the remap "
               "table of ", A.m, " entries");
   return std::make_tuple(wire, counts);
+}
+
+// One metric's table of a scan's extraction, to the wire form
+// (encode_table.h).  keys int32 [cap, MAX_KEY] (the u32 codes), counts
+// f64 [cap], str_off / str_len int32 per string id, blob the payload
+// bytes, numbers f64 per number id; n, n_str, used and n_num are int32
+// [1] on the device, as the extraction hands them out.  col_kind is per
+// breakdown: 0 plain, 1 date, 2 bucketized.  Returns (codes int64 [n,
+// nk], tagpack int64 [n], vals f64 [n], dict_blob uint8, dict_offs int64
+// [S_dev + 1], exc_kind int32 [E], exc_id int32 [E], exc_blob uint8,
+// exc_offs int64 [E + 1], refused): the exceptions have the wire string
+// codes S_dev + position and are the caller's to render and append.
+// refused: an integer column holds NaN or an infinity, nothing else is
+// returned and the host path answers.  Syncs once, after the scans, to
+// read the sizes and the status word; the copy and emit kernels are
+// enqueued behind that.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
+           torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
+           torch::Tensor, bool>
+encode_table(torch::Tensor keys, torch::Tensor counts, torch::Tensor n,
+             torch::Tensor str_off, torch::Tensor str_len,
+             torch::Tensor n_str, torch::Tensor blob, torch::Tensor used,
+             torch::Tensor numbers, torch::Tensor n_num,
+             std::vector<int64_t> col_kind) {
+  const char* fn = "encode_table";
+  const auto dev = keys.device();
+  const int64_t nk = (int64_t)col_kind.size();
+  TORCH_CHECK(nk >= 1 && nk <= MAX_KEY, fn, ": col_kind needs 1..",
+              (int)MAX_KEY, " entries");
+  for (int64_t k : col_kind)
+    TORCH_CHECK(k >= ENC_COL_PLAIN && k <= ENC_COL_BUCKET, fn,
+                ": a column kind is 0 (plain), 1 (date) or 2 (bucketized)");
+  check_arg(fn, "keys", keys, torch::kInt32, 2, dev);
+  TORCH_CHECK(keys.size(1) == MAX_KEY, fn, ": keys must be [cap, ",
+              (int)MAX_KEY, "]");
+  const int64_t cap = keys.size(0);
+  check_arg(fn, "counts", counts, torch::kFloat64, 1, dev);
+  TORCH_CHECK(counts.size(0) == cap, fn, ": keys has ", cap,
+              " rows, counts has ", counts.size(0));
+  check_arg(fn, "str_off", str_off, torch::kInt32, 1, dev);
+  check_arg(fn, "str_len", str_len, torch::kInt32, 1, dev);
+  TORCH_CHECK(str_off.size(0) == str_len.size(0), fn,
+              ": str_off and str_len differ in length");
+  check_arg(fn, "blob", blob, torch::kUInt8, 1, dev);
+  check_arg(fn, "numbers", numbers, torch::kFloat64, 1, dev);
+  for (auto* t : {&n, &n_str, &used, &n_num}) {
+    check_arg(fn, "n / n_str / used / n_num", *t, torch::kInt32, 1, dev);
+    TORCH_CHECK(t->numel() == 1, fn, ": n, n_str, used and n_num hold one "
+                "int32 each");
+  }
+  const int64_t str_cap = str_off.size(0), num_cap = numbers.size(0);
+  TORCH_CHECK(cap < ((int64_t)1 << 31), fn, ": cap exceeds 2^31 rows");
+
+  // the segments of the one scanned array, each a multiple of 8 long
+  const int64_t s8 = (str_cap + 7) / 8 * 8, n8 = (num_cap + 7) / 8 * 8;
+  EncArgs A = {};
+  int64_t at = 0;
+  for (int k = 0; k < ENC_SEGS; k++) {
+    A.seg[k] = (uint32_t)at;
+    const bool by_number = k == ENC_XNUM_F || k == ENC_XNUM_B ||
+                           k == ENC_INT_F || k == ENC_INT_B;
+    at += by_number ? n8 : s8;
+  }
+  A.seg[ENC_SEGS] = (uint32_t)at;
+  const int64_t total = at + 8;
+  // a segment's own total stays below 2^32: its differences are exact
+  TORCH_CHECK(total < ((int64_t)1 << 31) &&
+                  2 * blob.numel() + 17 * num_cap + 64 < ((int64_t)1 << 32),
+              fn, ": dictionaries too large for 32-bit offsets");
+  const int64_t nsums = (total + SORT_SCAN_TILE - 1) / SORT_SCAN_TILE;
+
+  c10::DeviceGuard guard(dev);
+  // 16-byte loads from the bases of keys and blob
+  if ((uintptr_t)keys.data_ptr() % 16 != 0) keys = keys.clone();
+  if ((uintptr_t)blob.data_ptr() % 16 != 0) blob = blob.clone();
+
+  const auto u8 = on_dev(dev, torch::kUInt8);
+  const auto i32 = on_dev(dev, torch::kInt32);
+  const auto i64 = on_dev(dev, torch::kInt64);
+  torch::Tensor sflags, nflags, scan, sums, meta;
+  allocating([&] {
+    sflags = torch::zeros({3, std::max<int64_t>(str_cap, 1)}, u8);
+    nflags = torch::zeros({2, std::max<int64_t>(num_cap, 1)}, u8);
+    scan = torch::zeros({total}, i32);
+    sums = torch::empty({nsums}, i32);
+    meta = torch::zeros({ENC_M_WORDS}, i32);
+  }, "cannot allocate the encode buffers (", total, " scan entries)");
+  A.keys = (const uint32_t*)keys.data_ptr();
+  A.counts = (const double*)counts.data_ptr();
+  A.n_ptr = (const uint32_t*)n.data_ptr();
+  A.cap = (uint32_t)cap;
+  A.str_off = (const uint32_t*)str_off.data_ptr();
+  A.str_len = (const uint32_t*)str_len.data_ptr();
+  A.n_str_ptr = (const uint32_t*)n_str.data_ptr();
+  A.str_cap = (uint32_t)str_cap;
+  A.blob = (const uint8_t*)blob.data_ptr();
+  A.used_ptr = (const uint32_t*)used.data_ptr();
+  A.blob_cap = (uint32_t)blob.numel();
+  A.numbers = (const double*)numbers.data_ptr();
+  A.n_num_ptr = (const uint32_t*)n_num.data_ptr();
+  A.num_cap = (uint32_t)num_cap;
+  A.nk = (int)nk;
+  for (int64_t j = 0; j < nk; j++) A.col_kind[j] = (uint8_t)col_kind[j];
+  A.str_used = (uint8_t*)sflags[0].data_ptr();
+  A.arr_used = (uint8_t*)sflags[1].data_ptr();
+  A.str_cls = (uint8_t*)sflags[2].data_ptr();
+  A.num_used = (uint8_t*)nflags[0].data_ptr();
+  A.num_cls = (uint8_t*)nflags[1].data_ptr();
+  A.scan = (uint32_t*)scan.data_ptr();
+  A.sums = (uint32_t*)sums.data_ptr();
+  A.meta = (uint32_t*)meta.data_ptr();
+
+  auto blocks = [](int64_t items) {
+    return (uint32_t)std::max<int64_t>((items + ENC_BLOCK - 1) / ENC_BLOCK, 1);
+  };
+  const uint32_t str_grid = std::min(blocks(str_cap), GRID_CAP);
+  launch("encode_mark", encode_mark_kernel,
+         dim3(std::min(blocks(cap), GRID_CAP)), dim3(ENC_BLOCK), 0, A);
+  launch("encode_classify", encode_classify_kernel, dim3(str_grid),
+         dim3(ENC_BLOCK), 0, A);
+  launch("encode_numbers", encode_numbers_kernel, dim3(blocks(num_cap)),
+         dim3(ENC_BLOCK), 0, A);
+  launch("sort_scan", sort_scan_kernel, dim3((uint32_t)nsums),
+         dim3(SORT_BLOCK), 0, A.scan, (uint32_t)total, A.sums);
+  launch("sort_scan_sums", sort_scan_sums_kernel, dim3(1), dim3(SORT_BLOCK),
+         0, A.sums, (uint32_t)nsums);
+  launch("encode_totals", encode_totals_kernel, dim3(1), dim3(64), 0, A);
+  auto host = meta.cpu();  // waits for the kernels
+  const uint32_t* mp = (const uint32_t*)host.data_ptr<int32_t>();
+  const uint32_t status = mp[ENC_M_STATUS];
+  TORCH_CHECK(!(status & ENC_BAD_TAG), fn, ": a key code has a tag its "
+              "column cannot hold (an ordinal outside a bucketized column, "
+              "a string or special in one, or an unknown special)");
+  TORCH_CHECK(!(status & ENC_BAD_ID), fn, ": a key code names a string or "
+              "number id beyond the dictionary (n_str / n_num)");
+  TORCH_CHECK(!(status & ENC_BAD_SPAN), fn, ": a referenced string's span "
+              "ends beyond the used payload bytes");
+  const int64_t rows = mp[ENC_M_N];
+  const int64_t sdev = mp[ENC_M_SDEV], E = mp[ENC_M_E];
+  torch::Tensor codes, tagpack, vals, dict_blob, dict_offs, exc_kind, exc_id,
+      exc_blob, exc_offs;
+  if (status & ENC_REFUSED) {
+    auto none = torch::empty({0}, i64);
+    return std::make_tuple(none, none, none, none, none, none, none, none,
+                           none, true);
+  }
+  allocating([&] {
+    codes = torch::empty({rows, nk}, i64);
+    tagpack = torch::empty({rows}, i64);
+    vals = torch::empty({rows}, on_dev(dev, torch::kFloat64));
+    dict_blob = torch::empty({(int64_t)mp[ENC_M_DBYTES]}, u8);
+    dict_offs = torch::empty({sdev + 1}, i64);
+    exc_kind = torch::empty({E}, i32);
+    exc_id = torch::empty({E}, i32);
+    exc_blob = torch::empty({(int64_t)mp[ENC_M_EBYTES]}, u8);
+    exc_offs = torch::empty({E + 1}, i64);
+  }, "cannot allocate the wire table (", rows, " rows, ", sdev + E,
+     " strings)");
+  A.codes = (long long*)codes.data_ptr();
+  A.tagpack = (long long*)tagpack.data_ptr();
+  A.vals = (double*)vals.data_ptr();
+  A.dict_blob = (uint8_t*)dict_blob.data_ptr();
+  A.dict_offs = (long long*)dict_offs.data_ptr();
+  A.exc_kind = (int*)exc_kind.data_ptr();
+  A.exc_id = (int*)exc_id.data_ptr();
+  A.exc_blob = (uint8_t*)exc_blob.data_ptr();
+  A.exc_offs = (long long*)exc_offs.data_ptr();
+  launch("encode_strings", encode_strings_kernel, dim3(str_grid),
+         dim3(ENC_BLOCK), 0, A);
+  launch("encode_digits", encode_digits_kernel, dim3(blocks(num_cap)),
+         dim3(ENC_BLOCK), 0, A);
+  if (rows > 0)
+    launch("encode_emit", encode_emit_kernel, dim3(blocks(rows)),
+           dim3(ENC_BLOCK), 0, A);
+  return std::make_tuple(codes, tagpack, vals, dict_blob, dict_offs, exc_kind,
+                         exc_id, exc_blob, exc_offs, false);
 }
 
 }  // namespace dn

@@ -22,7 +22,8 @@
 // merge_rows.h (device only: re-aggregation of merged multi-GPU tables),
 // sort_rows.h (device only: radix sort of the merged rows),
 // unify_strings.h (device only: one dictionary out of the ranks'),
-// partition_rows.h (device only: the rows of a rank split by destination).
+// partition_rows.h (device only: the rows of a rank split by destination),
+// encode_table.h (device only: a scan's tables to the merge's wire form).
 
 #include "common.h"
 #include <hip/hip_runtime.h>
@@ -609,5 +610,8 @@ __global__ void extract_numdict_kernel(NumDict D, double* out_vals,
 
 // stable split of a rank's rows by the rank that merges them; last again
 #include "partition_rows.h"
+
+// a scan's extraction to the wire form the merge reads; last again
+#include "encode_table.h"
 
 }  // extern "C++"
