@@ -40,6 +40,7 @@ import numpy as np
 from .merge import (_EL_STR, WireTable, _encode_table,  # noqa: F401
                     _group_rows, _np, _rebuild_table, _strings_blob,
                     encode_table, partition_rows, reaggregate,
+                    reaggregate_points,
                     unify_dictionaries)
 
 _PARTITION_ROWS = 1 << 20  # switch to hash-partition all_to_all above
@@ -127,13 +128,16 @@ def _gather_dictionaries(blob, soffs, ns_strs, ns_blob, device, group):
     return list(zip(g_blob, g_soffs))
 
 
-def merge_tables_tensor(agg, query, device=None, group=None):
+def merge_tables_tensor(agg, query, device=None, group=None,
+                        as_points=False):
     """Dense RCCL merge of one aggregation table (C1+C2); every rank
     returns the fully-merged Aggregator (allreduce semantics).  See
     module docstring for the wire format; no object serialization.
     agg is this rank's Aggregator, encoded here on the host, or its
     WireTable (merge.encode_table): one on the device is neither
-    encoded nor uploaded."""
+    encoded nor uploaded.  With as_points every rank returns the merged
+    table's points as NDJSON bytes instead (merge.reaggregate_points):
+    no Aggregator is built, so no counters travel with it."""
     import torch
     import torch.distributed as dist
 
@@ -160,7 +164,7 @@ def merge_tables_tensor(agg, query, device=None, group=None):
         dicts = _gather_dictionaries(blob, soffs, ns_strs, ns_blob, device,
                                      group)
         merged = _merge_partitioned(query, codes, tagpack, vals, dicts,
-                                    device, group)
+                                    device, group, as_points)
     else:
         g_codes = _all_gather_padded(
             _to_device(codes.reshape(-1), torch.int64, device),
@@ -178,13 +182,17 @@ def merge_tables_tensor(agg, query, device=None, group=None):
         # strings it needs
         parts = [(g_codes[r].reshape(int(ns_rows[r]), nk), g_tags[r],
                   g_vals[r]) for r in range(world)]
-        merged = reaggregate(query, parts, dicts, device=device)
+        merged = (reaggregate_points if as_points else reaggregate)(
+            query, parts, dicts, device=device)
+    if as_points:
+        return merged
     merged.ninputs = agg.ninputs  # per-rank; callers sum via counters
     merged.ndropped_nonnumeric = agg.ndropped_nonnumeric
     return merged
 
 
-def _merge_partitioned(query, codes, tagpack, vals, dicts, device, group):
+def _merge_partitioned(query, codes, tagpack, vals, dicts, device, group,
+                       as_points=False):
     """Pathological-cardinality path: hash-partition key rows across
     ranks with all_to_all_single (reduce-scatter shape — each rank
     merges one key range), then all_gather the merged partitions so
@@ -244,8 +252,8 @@ def _merge_partitioned(query, codes, tagpack, vals, dicts, device, group):
         group)
     # every partition is in global codes: each rank's "dictionary" is
     # the global one and its remap the identity
-    return reaggregate(query, [split(p) for p in parts],
-                       [gstrings] * world, device=device)
+    return (reaggregate_points if as_points else reaggregate)(
+        query, [split(p) for p in parts], [gstrings] * world, device=device)
 
 
 def merge_aggregators(aggs, queries, device=None, group=None):

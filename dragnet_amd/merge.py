@@ -26,6 +26,13 @@ and hands the gathered tensors to reaggregate().
      its hash names; remap, hash and a stable split by destination:
      numpy on the host, or the partition_rows kernels
      (ops/hip/partition_rows.h) with the remap table where unify left it.
+  render_points: the receiving end.  The distinct rows, their sums and
+     the global dictionary to the NDJSON point lines `dn scan --points`
+     prints: _decode_rows, Aggregator.points() and output.point_json per
+     row on the host, or, in the order sort_rows gives, the render_points
+     kernels (ops/hip/render_points.h), no row becoming a Python object.
+     reaggregate_points is reaggregate with that in place of
+     _decode_rows; DRAGNET_RENDER_GPU chooses.
   DRAGNET_UNIFY_GPU, DRAGNET_MERGE_GPU and DRAGNET_PARTITION_GPU choose
   (_use_gpu); the host and device paths give the same bits.
 """
@@ -344,14 +351,15 @@ def _group_rows_host(parts, remaps, nk):
     return _group_host(np.concatenate(all_rows), np.concatenate(all_vals))
 
 
-def _group_rows_device(parts, remaps, nk, device):
+def _group_rows_device(parts, remaps, nk, device, keep=False):
     """One merge_rows call over the parts as segments; the remap runs
     inside the kernel.  Parts already on the GPU are never copied to
     the host; only the distinct rows and their sums come back, already
     in np.unique's order (lexicographic over the columns left to right,
     as signed int64: the radix sort of ops/hip/sort_rows.h, behind
-    merge_rows' sort=True).  None when the kernel reports sums that
-    depend on the order of its adds."""
+    merge_rows' sort=True); with keep they stay device tensors, for
+    render_points.  None when the kernel reports sums that depend on
+    the order of its adds."""
     import torch
 
     from .ops import load_ops
@@ -378,10 +386,12 @@ def _group_rows_device(parts, remaps, nk, device):
     uniq, sums, exact = ops.merge_rows(rows, vals, nk, sort=True, **kw)
     if not exact:
         return None
+    if keep:
+        return uniq, sums
     return uniq.cpu().numpy(), sums.cpu().numpy()
 
 
-def _group_rows(parts, remaps, nk, device=None):
+def _group_rows(parts, remaps, nk, device=None, keep=False):
     """Group the rows [codes..., tagpack] of all parts and sum their
     values: (uniq [g, nk + 1], sums [g]) in np.unique's order.  remaps
     is one int64 table per part for its string-tagged codes, or None.
@@ -390,11 +400,12 @@ def _group_rows(parts, remaps, nk, device=None):
     come in no fixed order, and only sums of non-negative integers that
     stay below 2^53 are independent of the order, so the kernel reports
     anything else (a fractional, negative, NaN or infinite weight, a
-    value or a sum at or beyond 2^53) and the host path then answers."""
+    value or a sum at or beyond 2^53) and the host path then answers.
+    With keep the device path leaves both on the device."""
     n_rows = sum(int(p[1].shape[0]) for p in parts)
     out = None
     if _merge_on_gpu(n_rows, nk):
-        out = _group_rows_device(parts, remaps, nk, device)
+        out = _group_rows_device(parts, remaps, nk, device, keep)
     if out is None:
         out = _group_rows_host(parts, remaps, nk)
     return out
@@ -416,10 +427,11 @@ def _unify_on_gpu(dicts, n_strings):
         "DRAGNET_UNIFY_GPU", "DRAGNET_UNIFY_GPU_STRINGS", n_strings)
 
 
-def _unify_host(dicts):
+def _unify_host(dicts, as_blob=False):
     """FirstSeen over the strings' UTF-8 bytes (the encoding is
     one-to-one): the reference the device path must equal.  Wire-form
-    entries are sliced, not decoded; only the distinct strings are."""
+    entries are sliced, not decoded; only the distinct strings are, and
+    with as_blob not even those: they come back as (blob, offs)."""
     seen = FirstSeen()
     remaps = []
     for d in dicts:
@@ -429,14 +441,20 @@ def _unify_host(dicts):
         else:
             items = [s.encode("utf-8") for s in d]
         remaps.append(seen.ids(items))
+    if as_blob:
+        offs = np.zeros(len(seen.values) + 1, dtype=np.int64)
+        np.cumsum([len(b) for b in seen.values], out=offs[1:])
+        blob = np.frombuffer(b"".join(seen.values), dtype=np.uint8).copy()
+        return (blob, offs), remaps
     return [b.decode("utf-8") for b in seen.values], remaps
 
 
-def _unify_device(dicts, device):
+def _unify_device(dicts, device, as_blob=False):
     """One unify_strings call (ops/hip/unify_strings.h) over the blobs
     as one blob.  Blobs already on the GPU are never copied to the host;
     the remap tables stay on the device, and only the bytes of the G
-    first occurrences come back, to be decoded into gstrings."""
+    first occurrences come back, to be decoded into gstrings; with
+    as_blob they stay where they are packed, as (blob, offs)."""
     import torch
 
     from .ops import load_ops
@@ -462,6 +480,8 @@ def _unify_device(dicts, device):
     nbytes = int(goffs[-1])
     packed = blob[torch.repeat_interleave(shift, flen, output_size=nbytes)
                   + torch.arange(nbytes, device=device)]
+    if as_blob:
+        return (packed, torch.cat([fend.new_zeros(1), fend])), remaps
     return _decode_strings(packed.cpu().numpy().tobytes(), goffs), remaps
 
 
@@ -476,11 +496,17 @@ def unify_dictionaries(dicts, device=None):
     unify_strings kernels number the spans where the gather left them
     and the remaps stay device tensors for merge_rows.  Either way only
     the distinct strings are decoded, and both give the same result."""
+    return _unify(dicts, device)
+
+
+def _unify(dicts, device, as_blob=False):
+    """unify_dictionaries; with as_blob the distinct strings come back
+    in wire form, (blob, offs), where the path that ran leaves them."""
     n_strings = sum(max(len(d[1]) - 1, 0) if _is_blob_pair(d) else len(d)
                     for d in dicts)
     if _unify_on_gpu(dicts, n_strings):
-        return _unify_device(dicts, device)
-    return _unify_host(dicts)
+        return _unify_device(dicts, device, as_blob)
+    return _unify_host(dicts, as_blob)
 
 
 # ---- partition by destination rank ---------------------------------------
@@ -573,3 +599,138 @@ def reaggregate(query, parts, strings_per_part, device=None):
     gstrings, remaps = unify_dictionaries(strings_per_part, device)
     uniq, sums = _group_rows(parts, remaps, nk, device)
     return _decode_rows(query, uniq, sums, gstrings)
+
+
+# ---- the receiving end: rows to point lines -------------------------------
+
+def _points_bytes(agg):
+    """An Aggregator's points as NDJSON, json.dumps per point: what
+    output.output_points writes."""
+    from .output import point_json
+    return "".join(point_json(p) + "\n" for p in agg.points()).encode()
+
+
+def _render_host(query, uniq, sums, strings):
+    """_decode_rows, Aggregator.points() and output.point_json per row:
+    the definition the device path must equal byte for byte."""
+    if _is_blob_pair(strings):
+        strings = _decode_strings(_np(strings[0]).tobytes(),
+                                  _np(strings[1]).tolist())
+    return _points_bytes(_decode_rows(query, _np(uniq), _np(sums), strings))
+
+
+def _render_device(query, uniq, sums, strings, device):
+    """The render_points kernels (ops/hip/render_points.h) on the rows
+    where they lie: the NDJSON bytes, or None where the table is one
+    only the host renders (rows of different tag packs, an F64 tag,
+    numbers beyond int64, a fractional sum, two breakdowns of one name,
+    one string twice in the dictionary).
+
+    Line order is Aggregator.points()'s: integers by value, strings by
+    code point, which is UTF-8 byte order.  The rank of each dictionary
+    string in that order is computed on the host for now, one C-level
+    sort over the G distinct byte strings; a device gather puts the
+    ranks in place of the codes of the string columns and sort_rows
+    orders those nk columns."""
+    import json
+
+    import torch
+
+    from .ops import load_ops
+    from .points import fast_reduce_spec
+    ops = load_ops(required=True)  # a missing extension is an error
+    nk = len(query.breakdowns)
+    spec = fast_reduce_spec(query)
+    names = [name for name, _kind, _step in spec]
+    if len(set(names)) != nk:
+        return None
+    device, up = _work_device(device, [uniq, sums])
+    rows = up(uniq, torch.int64).contiguous()
+    tags = rows[:, nk]
+    tp = int(tags[0])
+    if bool((tags != tp).any()):
+        return None
+    el = [(tp >> (2 * j)) & 3 for j in range(nk)]
+    if any(e not in (_EL_INT, _EL_STR) for e in el):
+        return None
+    keys = rows[:, :nk].contiguous()
+    if _EL_STR in el:
+        if _is_blob_pair(strings):
+            raw, at = _np(strings[0]).tobytes(), _np(strings[1]).tolist()
+            items = [raw[a:b] for a, b in zip(at, at[1:])]
+            blob, offs = strings
+        else:
+            items = [s.encode("utf-8") for s in strings]
+            blob, offs = _strings_blob(strings)
+            blob = np.frombuffer(blob, dtype=np.uint8).copy()
+        n_str = len(items)
+        if len(set(items)) != n_str:
+            return None
+        if n_str:  # none: every code is out of range, and the op says so
+            rank = np.empty(n_str, dtype=np.int64)
+            rank[sorted(range(n_str), key=items.__getitem__)] = \
+                np.arange(n_str)
+            rank = up(rank, torch.int64)
+            for j in range(nk):
+                if el[j] == _EL_STR:  # a bad code is the op's to report
+                    keys[:, j] = rank[keys[:, j].clamp(0, n_str - 1)]
+    else:
+        blob, offs = np.zeros(0, np.uint8), np.zeros(1, np.int64)
+    order = ops.sort_rows(keys)
+    segs = ['{"fields":{' + json.dumps(names[0]) + ":"]
+    segs += ["," + json.dumps(name) + ":" for name in names[1:]]
+    segs += ['},"value":', "}\n"]
+    segs = [t.encode() for t in segs]
+    seg_offs = np.concatenate([[0], np.cumsum([len(t) for t in segs])])
+    text, _line_off, refused = ops.render_points(
+        rows, up(sums, torch.float64).contiguous(), order,
+        up(blob, torch.uint8).reshape(-1).contiguous(),
+        up(offs, torch.int64).reshape(-1).contiguous(),
+        [kind for _name, kind, _step in spec],
+        [int(step) for _name, _kind, step in spec],
+        up(np.frombuffer(b"".join(segs), dtype=np.uint8).copy(), torch.uint8),
+        up(seg_offs, torch.int64))
+    return None if refused else text.cpu().numpy().tobytes()
+
+
+def render_points(query, uniq, sums, strings, device=None):
+    """The receiving end's one seam: distinct rows uniq [g, nk + 1]
+    (key codes, then the tag pack) and their sums [g] as _group_rows
+    returns them, numpy or torch on any device, and the dictionary the
+    string codes index, a list of str or a (blob, offs) pair, to the
+    NDJSON bytes output_points(agg.points()) writes for the Aggregator
+    _decode_rows builds from them.
+
+    The host path builds exactly that (_render_host); the device path is
+    the render_points kernels (_render_device) and gives the same bytes,
+    or hands a table it cannot render to the host path whole.
+    DRAGNET_RENDER_GPU and DRAGNET_RENDER_GPU_ROWS distinct rows choose
+    (_use_gpu; infinity by default: profiles/r14_render_points.md).  A
+    table without breakdowns is one scalar and stays on the host."""
+    nk = len(query.breakdowns)
+    g = int(uniq.shape[0])
+    out = None
+    if nk >= 1 and _use_gpu("DRAGNET_RENDER_GPU", "DRAGNET_RENDER_GPU_ROWS",
+                            g):
+        out = _render_device(query, uniq, sums, strings, device)
+    if out is None:
+        out = _render_host(query, uniq, sums, strings)
+    return out
+
+
+def reaggregate_points(query, parts, strings_per_part, device=None):
+    """reaggregate with render_points in place of _decode_rows: the
+    merged table as NDJSON bytes, one point per line, in
+    Aggregator.points()'s order.  Where the group step and the render
+    step both run on the device the distinct rows and their sums stay
+    there between them, and the global dictionary stays in wire form
+    wherever unify_dictionaries left it."""
+    nk = len(query.breakdowns)
+    if nk == 0:
+        vals = [_np(v).astype(np.float64, copy=False)
+                for _c, _t, v in parts]
+        return _points_bytes(_scalar_table(
+            query, np.concatenate(vals) if vals else np.zeros(0)))
+    gstrings, remaps = _unify(strings_per_part, device, as_blob=True)
+    uniq, sums = _group_rows(parts, remaps, nk, device, keep=True)
+    return render_points(query, uniq, sums, gstrings, device)

@@ -1,6 +1,6 @@
 // What the scan layer (scan_*.h) and the merge layer (merge_rows.h,
-// sort_rows.h, unify_strings.h, partition_rows.h, encode_table.h) share,
-// and nothing else: the hash
+// sort_rows.h, unify_strings.h, partition_rows.h, encode_table.h,
+// render_points.h) share, and nothing else: the hash
 // finisher, the relaxed atomics of the claim-and-publish tables, and the
 // segment search.  The first part is plain C++17 under a host compiler
 // (scan_text.h includes it); the second is device only.

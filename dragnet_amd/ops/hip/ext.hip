@@ -110,7 +110,8 @@ ScanKernel xpose_kernel(int mw, int xg) {
 }  // namespace
 }  // namespace dn
 
-// sort_rows, merge_rows, unify_strings, partition_rows, encode_table
+// sort_rows, merge_rows, unify_strings, partition_rows, encode_table,
+// render_points
 #include "ext_merge.h"
 
 namespace dn {
@@ -747,6 +748,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "one metric of a scan's extraction to the wire form -> (codes, "
         "tagpack, vals, dict_blob, dict_offs, exc_kind, exc_id, exc_blob, "
         "exc_offs, refused)");
+  m.def("render_points", &dn::render_points, py::arg("rows"),
+        py::arg("sums"), py::arg("order"), py::arg("dict_blob"),
+        py::arg("dict_offs"), py::arg("col_kind"), py::arg("col_step"),
+        py::arg("seg_blob"), py::arg("seg_offs"),
+        "merged rows as NDJSON point lines, line i being row order[i] -> "
+        "(text uint8, line_off int64 [g + 1], refused)");
   m.def("lds_bytes", &dn::lds_bytes, py::arg("nf"), py::arg("nm"),
         py::arg("ns") = 0, py::arg("columnar") = false,
         "dynamic LDS bytes of a scan / columnar launch (host only)");

@@ -1,8 +1,8 @@
 // Host bindings of the merge layer, the step after the multi-GPU gather
 // (dragnet_amd/merge.py): sort_rows (sort_rows.h), merge_rows
 // (merge_rows.h), unify_strings (unify_strings.h), partition_rows
-// (partition_rows.h) and encode_table (encode_table.h), free functions
-// that keep nothing between calls.
+// (partition_rows.h), encode_table (encode_table.h) and render_points
+// (render_points.h), free functions that keep nothing between calls.
 // Part of ext.hip's translation unit, behind its launch plumbing (launch,
 // on_dev, allocating, GRID_CAP).
 #pragma once
@@ -639,6 +639,165 @@ encode_table(torch::Tensor keys, torch::Tensor counts, torch::Tensor n,
            dim3(ENC_BLOCK), 0, A);
   return std::make_tuple(codes, tagpack, vals, dict_blob, dict_offs, exc_kind,
                          exc_id, exc_blob, exc_offs, false);
+}
+
+// The merged table as NDJSON point lines (render_points.h): rows int64
+// [g, nk + 1] (key codes, then the tag pack) and sums f64 [g] as
+// merge_rows leaves them; order int32 [g] (none: row order), line i being
+// row order[i]; dict_blob / dict_offs int64 [G + 1] the global dictionary
+// in wire form; col_kind per breakdown 0 plain, 1 date, 2 quantize, 3
+// lquantize with col_step its step; seg_blob / seg_offs int64 [nk + 3] the
+// nk + 2 constant pieces of a line.  Returns (text uint8
+// [bytes], line_off int64 [g + 1], refused).  refused: some element or
+// value is one only Python renders (beyond int64, fractional, NaN,
+// infinite, F64-tagged) or the dictionary is too large for 32-bit
+// offsets; the tensors are empty and the host path answers.  g == 0
+// launches nothing.  Syncs once, after the measuring kernels, to read the
+// status word and the two byte totals; the escape and emit kernels are
+// enqueued behind that.
+std::tuple<torch::Tensor, torch::Tensor, bool> render_points(
+    torch::Tensor rows, torch::Tensor sums,
+    c10::optional<torch::Tensor> order, torch::Tensor dict_blob,
+    torch::Tensor dict_offs, std::vector<int64_t> col_kind,
+    std::vector<int64_t> col_step, torch::Tensor seg_blob,
+    torch::Tensor seg_offs) {
+  const char* fn = "render_points";
+  const auto dev = rows.device();
+  const int64_t nk = (int64_t)col_kind.size();
+  TORCH_CHECK(nk >= 1 && nk <= MAX_KEY, fn, ": col_kind needs 1..",
+              (int)MAX_KEY, " entries");
+  TORCH_CHECK((int64_t)col_step.size() == nk, fn,
+              ": col_kind and col_step differ in length");
+  for (int64_t k : col_kind)
+    TORCH_CHECK(k >= REN_COL_PLAIN && k <= REN_COL_LQUANTIZE, fn,
+                ": a column kind is 0 (plain), 1 (date), 2 (quantize) or 3 "
+                "(lquantize)");
+  check_arg(fn, "rows", rows, torch::kInt64, 2, dev);
+  TORCH_CHECK(rows.size(1) == nk + 1, fn, ": rows must be [g, nk + 1]");
+  const int64_t g = rows.size(0);
+  check_arg(fn, "sums", sums, torch::kFloat64, 1, dev);
+  TORCH_CHECK(sums.size(0) == g, fn, ": rows has ", g, " rows, sums has ",
+              sums.size(0));
+  if (order.has_value()) {
+    check_arg(fn, "order", *order, torch::kInt32, 1, dev);
+    TORCH_CHECK(order->size(0) == g, fn, ": rows has ", g,
+                " rows, order has ", order->size(0));
+  }
+  check_arg(fn, "dict_blob", dict_blob, torch::kUInt8, 1, dev);
+  check_arg(fn, "dict_offs", dict_offs, torch::kInt64, 1, dev);
+  TORCH_CHECK(dict_offs.size(0) >= 1, fn, ": dict_offs needs G + 1 entries");
+  const int64_t G = dict_offs.size(0) - 1;
+  TORCH_CHECK(g < ((int64_t)1 << 31) && G < ((int64_t)1 << 31), fn,
+              ": more than 2^31 rows or strings");
+  check_arg(fn, "seg_blob", seg_blob, torch::kUInt8, 1, dev);
+  check_arg(fn, "seg_offs", seg_offs, torch::kInt64, 1, dev);
+  TORCH_CHECK(seg_offs.size(0) == nk + 3 &&
+                  seg_blob.numel() < (int64_t)REN_MAX_LINE,
+              fn, ": seg_offs needs nk + 3 entries and seg_blob fewer than ",
+              REN_MAX_LINE, " bytes");
+  RenArgs A = {};
+  const auto u8 = on_dev(dev, torch::kUInt8);
+  const auto i64 = on_dev(dev, torch::kInt64);
+  if (g == 0)
+    return std::make_tuple(torch::empty({0}, u8), torch::zeros({1}, i64),
+                           false);
+  auto none = [&] {
+    return std::make_tuple(torch::empty({0}, u8), torch::empty({0}, i64),
+                           true);
+  };
+  // the escaped dictionary is at most this long and is offset in u32
+  if (6 * dict_blob.numel() + 2 * G + 64 >= ((int64_t)1 << 32)) return none();
+
+  c10::DeviceGuard guard(dev);
+  // 16-byte loads from the base of dict_blob
+  if ((uintptr_t)dict_blob.data_ptr() % 16 != 0) dict_blob = dict_blob.clone();
+
+  const int64_t G8 = (G + 1 + 7) / 8 * 8, g8 = (g + 1 + 7) / 8 * 8;
+  const int64_t esc_nsums = (G8 + SORT_SCAN_TILE - 1) / SORT_SCAN_TILE;
+  const int64_t line_nsums = (g8 + SORT_SCAN_TILE - 1) / SORT_SCAN_TILE;
+  const auto i32 = on_dev(dev, torch::kInt32);
+  torch::Tensor esc_scan, esc_sums, line_scan, line_sums, line_base,
+      meta;
+  allocating([&] {
+    esc_scan = torch::zeros({G8}, i32);
+    esc_sums = torch::empty({esc_nsums}, i32);
+    line_scan = torch::zeros({g8}, i32);
+    line_sums = torch::empty({line_nsums}, i32);
+    line_base = torch::empty({line_nsums}, i64);
+    meta = torch::zeros({REN_M_WORDS}, i64);
+  }, "cannot allocate the render buffers (", G8 + g8, " scan entries)");
+  A.rows = (const long long*)rows.data_ptr();
+  A.sums = (const double*)sums.data_ptr();
+  A.order = order.has_value() ? (const uint32_t*)order->data_ptr() : nullptr;
+  A.g = (uint32_t)g;
+  A.nk = (int)nk;
+  A.dict_blob = (const uint8_t*)dict_blob.data_ptr();
+  A.dict_len = dict_blob.numel();
+  A.dict_offs = (const long long*)dict_offs.data_ptr();
+  A.G = (uint32_t)G;
+  for (int64_t j = 0; j < nk; j++) {
+    A.col_kind[j] = (uint8_t)col_kind[j];
+    A.col_step[j] = (long long)col_step[j];
+  }
+  A.seg_blob = (const uint8_t*)seg_blob.data_ptr();
+  A.seg_len = seg_blob.numel();
+  A.seg_offs = (const long long*)seg_offs.data_ptr();
+  A.esc_scan = (uint32_t*)esc_scan.data_ptr();
+  A.esc_sums = (uint32_t*)esc_sums.data_ptr();
+  A.line_scan = (uint32_t*)line_scan.data_ptr();
+  A.line_sums = (uint32_t*)line_sums.data_ptr();
+  A.line_nsums = (uint32_t)line_nsums;
+  A.line_base = (long long*)line_base.data_ptr();
+  A.meta = (unsigned long long*)meta.data_ptr();
+
+  auto blocks = [](int64_t items) {
+    return dim3((uint32_t)((items + REN_BLOCK - 1) / REN_BLOCK));
+  };
+  if (G > 0)
+    launch("render_escape_measure", render_escape_measure_kernel, blocks(G),
+           dim3(REN_BLOCK), 0, A);
+  launch("sort_scan", sort_scan_kernel, dim3((uint32_t)esc_nsums),
+         dim3(SORT_BLOCK), 0, A.esc_scan, (uint32_t)G8, A.esc_sums);
+  launch("sort_scan_sums", sort_scan_sums_kernel, dim3(1), dim3(SORT_BLOCK), 0,
+         A.esc_sums, (uint32_t)esc_nsums);
+  launch("render_measure", render_measure_kernel, blocks(g), dim3(REN_BLOCK),
+         0, A);
+  launch("sort_scan", sort_scan_kernel, dim3((uint32_t)line_nsums),
+         dim3(SORT_BLOCK), 0, A.line_scan, (uint32_t)g8, A.line_sums);
+  launch("render_totals", render_totals_kernel, dim3(1), dim3(SORT_BLOCK), 0,
+         A);
+  auto host = meta.cpu();  // waits for the kernels
+  const int64_t* mp = host.data_ptr<int64_t>();
+  const uint32_t status = (uint32_t)mp[REN_M_STATUS];
+  TORCH_CHECK(!(status & REN_BAD_DICT), fn, ": dict_offs does not ascend "
+              "from 0 within the ", dict_blob.numel(), " bytes of dict_blob");
+  TORCH_CHECK(!(status & REN_BAD_UTF8), fn, ": a dictionary string is "
+              "ill-formed UTF-8");
+  TORCH_CHECK(!(status & REN_BAD_SEG), fn, ": seg_offs does not ascend from "
+              "0 to the ", seg_blob.numel(), " bytes of seg_blob");
+  TORCH_CHECK(!(status & REN_BAD_ORDER), fn, ": an order entry lies outside "
+              "the ", g, " rows");
+  TORCH_CHECK(!(status & REN_BAD_TAG), fn, ": a key element's tag is none of "
+              "INT, STR and F64");
+  TORCH_CHECK(!(status & REN_BAD_CODE), fn, ": a string-tagged code lies "
+              "outside the dictionary of ", G, " strings");
+  if (status & REN_REFUSED) return none();
+  torch::Tensor esc_blob, text, line_off;
+  allocating([&] {
+    esc_blob = torch::empty({mp[REN_M_ESC_BYTES]}, u8);
+    text = torch::empty({mp[REN_M_TEXT_BYTES]}, u8);
+    line_off = torch::empty({g + 1}, i64);
+  }, "cannot allocate the point lines (", mp[REN_M_TEXT_BYTES], " bytes for ",
+     g, " rows)");
+  A.esc_blob = (uint8_t*)esc_blob.data_ptr();
+  A.esc_len = esc_blob.numel();
+  A.text = (uint8_t*)text.data_ptr();
+  A.line_off = (long long*)line_off.data_ptr();
+  if (G > 0)
+    launch("render_escape", render_escape_kernel, blocks(G), dim3(REN_BLOCK),
+           0, A);
+  launch("render_emit", render_emit_kernel, blocks(g), dim3(REN_BLOCK), 0, A);
+  return std::make_tuple(text, line_off, false);
 }
 
 }  // namespace dn

@@ -23,7 +23,8 @@
 // sort_rows.h (device only: radix sort of the merged rows),
 // unify_strings.h (device only: one dictionary out of the ranks'),
 // partition_rows.h (device only: the rows of a rank split by destination),
-// encode_table.h (device only: a scan's tables to the merge's wire form).
+// encode_table.h (device only: a scan's tables to the merge's wire form),
+// render_points.h (device only: the merged rows as NDJSON point lines).
 
 #include "common.h"
 #include <hip/hip_runtime.h>
@@ -613,5 +614,8 @@ __global__ void extract_numdict_kernel(NumDict D, double* out_vals,
 
 // a scan's extraction to the wire form the merge reads; last again
 #include "encode_table.h"
+
+// the merged rows as the point lines `dn scan --points` prints; last again
+#include "render_points.h"
 
 }  // extern "C++"
