@@ -33,6 +33,10 @@ and hands the gathered tensors to reaggregate().
      kernels (ops/hip/render_points.h), no row becoming a Python object.
      reaggregate_points is reaggregate with that in place of
      _decode_rows; DRAGNET_RENDER_GPU chooses.
+  rank_strings: what orders those lines by string, the rank of every
+     dictionary string in byte order: one sorted() over the bytes on the
+     host, or the rank_strings kernels (ops/hip/rank_strings.h) on the
+     dictionary where it lies; DRAGNET_RANK_GPU chooses.
   DRAGNET_UNIFY_GPU, DRAGNET_MERGE_GPU and DRAGNET_PARTITION_GPU choose
   (_use_gpu); the host and device paths give the same bits.
 """
@@ -619,6 +623,57 @@ def _render_host(query, uniq, sums, strings):
     return _points_bytes(_decode_rows(query, _np(uniq), _np(sums), strings))
 
 
+def _rank_host(strings):
+    """The ranks on the host: the G byte strings as slices, a set to see
+    whether one occurs twice, one C-level sort.  The reference the device
+    path must equal."""
+    if _is_blob_pair(strings):
+        raw, at = _np(strings[0]).tobytes(), _np(strings[1]).tolist()
+        items = [raw[a:b] for a, b in zip(at, at[1:])]
+    else:
+        items = [s.encode("utf-8") for s in strings]
+    n_str = len(items)
+    if len(set(items)) != n_str:
+        return None
+    rank = np.empty(n_str, dtype=np.int64)
+    rank[sorted(range(n_str), key=items.__getitem__)] = np.arange(n_str)
+    return rank
+
+
+def _rank_device(strings, device):
+    """One rank_strings call (ops/hip/rank_strings.h) on the dictionary
+    where it lies; the ranks stay on the device."""
+    import torch
+
+    from .ops import load_ops
+    ops = load_ops(required=True)  # a missing extension is an error
+    if not _is_blob_pair(strings):
+        blob, offs = _strings_blob(strings)
+        strings = np.frombuffer(blob, dtype=np.uint8).copy(), offs
+    device, up = _work_device(device, list(strings))
+    rank, twice = ops.rank_strings(
+        up(strings[0], torch.uint8).reshape(-1).contiguous(),
+        up(strings[1], torch.int64).reshape(-1).contiguous())
+    return None if twice else rank
+
+
+def rank_strings(strings, device=None):
+    """The rank of every dictionary string in byte order, which for UTF-8
+    is code point order, Aggregator.points()'s: int64 [G], rank[i] = the
+    number of strings smaller than string i; None when a string occurs
+    twice.  strings is a list of str or a (blob, offs) pair, numpy or
+    torch on any device.  On the host (_rank_host) the result is numpy;
+    on the GPU (_rank_device, the rank_strings kernels) no dictionary
+    byte leaves the device and the ranks stay there.
+    DRAGNET_RANK_GPU and DRAGNET_RANK_GPU_STRINGS strings choose
+    (_use_gpu; infinity by default: profiles/r15_rank_strings.md)."""
+    n_str = max(len(strings[1]) - 1, 0) if _is_blob_pair(strings) \
+        else len(strings)
+    if _use_gpu("DRAGNET_RANK_GPU", "DRAGNET_RANK_GPU_STRINGS", n_str):
+        return _rank_device(strings, device)
+    return _rank_host(strings)
+
+
 def _render_device(query, uniq, sums, strings, device):
     """The render_points kernels (ops/hip/render_points.h) on the rows
     where they lie: the NDJSON bytes, or None where the table is one
@@ -627,11 +682,10 @@ def _render_device(query, uniq, sums, strings, device):
     one string twice in the dictionary).
 
     Line order is Aggregator.points()'s: integers by value, strings by
-    code point, which is UTF-8 byte order.  The rank of each dictionary
-    string in that order is computed on the host for now, one C-level
-    sort over the G distinct byte strings; a device gather puts the
-    ranks in place of the codes of the string columns and sort_rows
-    orders those nk columns."""
+    code point, which is UTF-8 byte order.  rank_strings gives the rank
+    of each dictionary string in that order, on the host or by the
+    rank_strings kernels; a device gather puts the ranks in place of the
+    codes of the string columns and sort_rows orders those nk columns."""
     import json
 
     import torch
@@ -656,20 +710,15 @@ def _render_device(query, uniq, sums, strings, device):
     keys = rows[:, :nk].contiguous()
     if _EL_STR in el:
         if _is_blob_pair(strings):
-            raw, at = _np(strings[0]).tobytes(), _np(strings[1]).tolist()
-            items = [raw[a:b] for a, b in zip(at, at[1:])]
             blob, offs = strings
         else:
-            items = [s.encode("utf-8") for s in strings]
             blob, offs = _strings_blob(strings)
             blob = np.frombuffer(blob, dtype=np.uint8).copy()
-        n_str = len(items)
-        if len(set(items)) != n_str:
+        n_str = max(len(offs) - 1, 0)
+        rank = rank_strings((blob, offs), device)
+        if rank is None:
             return None
         if n_str:  # none: every code is out of range, and the op says so
-            rank = np.empty(n_str, dtype=np.int64)
-            rank[sorted(range(n_str), key=items.__getitem__)] = \
-                np.arange(n_str)
             rank = up(rank, torch.int64)
             for j in range(nk):
                 if el[j] == _EL_STR:  # a bad code is the op's to report

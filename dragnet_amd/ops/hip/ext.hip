@@ -111,7 +111,7 @@ ScanKernel xpose_kernel(int mw, int xg) {
 }  // namespace dn
 
 // sort_rows, merge_rows, unify_strings, partition_rows, encode_table,
-// render_points
+// render_points, rank_strings
 #include "ext_merge.h"
 
 namespace dn {
@@ -754,6 +754,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("seg_blob"), py::arg("seg_offs"),
         "merged rows as NDJSON point lines, line i being row order[i] -> "
         "(text uint8, line_off int64 [g + 1], refused)");
+  m.def("rank_strings", &dn::rank_strings, py::arg("blob"), py::arg("offs"),
+        py::arg("finish_max") = (int)dn::RANK_FINISH_MAX,
+        "rank of every string of a wire-form dictionary in byte order -> "
+        "(rank int64 [G], duplicate)");
   m.def("lds_bytes", &dn::lds_bytes, py::arg("nf"), py::arg("nm"),
         py::arg("ns") = 0, py::arg("columnar") = false,
         "dynamic LDS bytes of a scan / columnar launch (host only)");
@@ -794,5 +798,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("UNIFY_TILE") = (int)dn::UNIFY_TILE;
   m.attr("UNIFY_STAGE_BYTES") = (int)dn::UNIFY_STAGE_BYTES;
   m.attr("ENC_STAGE_BYTES") = (int)dn::ENC_STAGE_BYTES;
+  m.attr("RANK_FINISH_MAX") = (int)dn::RANK_FINISH_MAX;
   m.attr("MAX_FIELDS") = (int)dn::MAX_FIELDS;
 }

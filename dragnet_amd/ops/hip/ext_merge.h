@@ -1,8 +1,9 @@
 // Host bindings of the merge layer, the step after the multi-GPU gather
 // (dragnet_amd/merge.py): sort_rows (sort_rows.h), merge_rows
 // (merge_rows.h), unify_strings (unify_strings.h), partition_rows
-// (partition_rows.h), encode_table (encode_table.h) and render_points
-// (render_points.h), free functions that keep nothing between calls.
+// (partition_rows.h), encode_table (encode_table.h), render_points
+// (render_points.h) and rank_strings (rank_strings.h), free functions that
+// keep nothing between calls.
 // Part of ext.hip's translation unit, behind its launch plumbing (launch,
 // on_dev, allocating, GRID_CAP).
 #pragma once
@@ -798,6 +799,147 @@ std::tuple<torch::Tensor, torch::Tensor, bool> render_points(
            0, A);
   launch("render_emit", render_emit_kernel, blocks(g), dim3(REN_BLOCK), 0, A);
   return std::make_tuple(text, line_off, false);
+}
+
+// The rank of every string of a dictionary in byte order
+// (rank_strings.h): blob uint8 [bytes], offs int64 [G + 1] ascending from
+// 0 within the blob.  Returns (rank int64 [G], duplicate): rank[i] is the
+// number of strings smaller than string i, bytes unsigned, a prefix
+// first; duplicate: some string occurs twice, the ranks are then
+// unspecified and the caller ranks on the host.  finish_max is the
+// largest tied group the finish kernel takes (RANK_FINISH_MAX; another
+// value is for measurements, 0 never runs it).  G == 0 launches nothing.
+// Syncs once in front of each round of 7 string bytes, to read the
+// round's active count, the span of its rows and the status word; once
+// more when that copy shows the sort over (no string still tied), or,
+// where the finish kernel ends it, behind that kernel.
+std::tuple<torch::Tensor, bool> rank_strings(torch::Tensor blob,
+                                             torch::Tensor offs,
+                                             int64_t finish_max) {
+  const char* fn = "rank_strings";
+  const auto dev = blob.device();
+  check_arg(fn, "blob", blob, torch::kUInt8, 1, dev);
+  check_arg(fn, "offs", offs, torch::kInt64, 1, dev);
+  TORCH_CHECK(offs.size(0) >= 1, fn, ": offs needs G + 1 entries");
+  const int64_t G = offs.size(0) - 1;
+  TORCH_CHECK(G < ((int64_t)1 << 31) - 16, fn, ": more than 2^31 strings");
+  TORCH_CHECK(finish_max >= 0, fn, ": finish_max is negative");
+  const auto i32 = on_dev(dev, torch::kInt32);
+  const auto i64 = on_dev(dev, torch::kInt64);
+  if (G == 0) return std::make_tuple(torch::empty({0}, i64), false);
+
+  c10::DeviceGuard guard(dev);
+  // aligned 8-byte words from the base of blob, the last one whole
+  const int64_t bytes = blob.numel();
+  if ((uintptr_t)blob.data_ptr() % 16 != 0 || bytes % 8 != 0) {
+    auto padded = torch::empty({(bytes + 7) / 8 * 8},
+                               on_dev(dev, torch::kUInt8));
+    padded.narrow(0, 0, bytes).copy_(blob);
+    blob = padded;
+  }
+
+  const int64_t G8 = (G + 1 + 7) / 8 * 8;
+  const int64_t nsums = (2 * G8 + SORT_SCAN_TILE - 1) / SORT_SCAN_TILE;
+  torch::Tensor rank, rows, scan, sums, sid, headpos, act[2], grp[2],
+      gstart[2], meta;
+  allocating([&] {
+    rank = torch::empty({G}, i64);
+    rows = torch::empty({G, 2}, i64);
+    scan = torch::empty({2 * G8}, i32);
+    sums = torch::empty({nsums}, i32);
+    sid = torch::empty({G}, i32);
+    headpos = torch::empty({G + 1}, i32);
+    for (int k = 0; k < 2; k++) {
+      act[k] = torch::empty({G}, i32);
+      grp[k] = torch::empty({G}, i32);
+      gstart[k] = torch::empty({G}, i32);
+    }
+    meta = torch::zeros({RANK_M_WORDS}, i64);
+    meta.narrow(0, RANK_M_SPAN, 2).fill_(-1);
+    meta.narrow(0, RANK_M_COUNT, 1).fill_(G);
+  }, "cannot allocate the rank buffers (", G, " strings)");
+  const uint64_t* words = (const uint64_t*)blob.data_ptr();
+  const long long* offs_p = (const long long*)offs.data_ptr();
+  long long* rows_p = (long long*)rows.data_ptr();
+  uint32_t* scan_p = (uint32_t*)scan.data_ptr();
+  uint32_t* sums_p = (uint32_t*)sums.data_ptr();
+  uint32_t* sid_p = (uint32_t*)sid.data_ptr();
+  uint32_t* head_p = (uint32_t*)headpos.data_ptr();
+  unsigned long long* meta_p = (unsigned long long*)meta.data_ptr();
+  auto u32 = [](torch::Tensor& t) { return (uint32_t*)t.data_ptr(); };
+  auto blocks = [](int64_t items) {
+    return dim3((uint32_t)((items + RANK_BLOCK - 1) / RANK_BLOCK));
+  };
+  // the rows of the active list `cur` (none: round 0) at `depth`, at most
+  // cap of them, and the bytes of theirs that vary
+  auto keys_and_span = [&](int cur, int64_t cap, int64_t depth) {
+    launch("rank_key", rank_key_kernel, blocks(cap), dim3(RANK_BLOCK), 0,
+           words, (long long)bytes, offs_p,
+           cur < 0 ? (const uint32_t*)nullptr : (const uint32_t*)u32(act[cur]),
+           cur < 0 ? (const uint32_t*)nullptr : (const uint32_t*)u32(grp[cur]),
+           (uint32_t)cap, (long long)depth, (longlong2*)rows_p, meta_p);
+    launch("sort_span", sort_span_kernel, dim3(sort_span_grid(cap)),
+           dim3(SORT_BLOCK), 0, (const long long*)rows_p, (uint32_t)cap,
+           (const uint32_t*)(meta_p + RANK_M_COUNT), 2, meta_p + RANK_M_SPAN);
+  };
+
+  int cur = -1;  // the active list's buffers; -1: every string, round 0
+  int64_t m = G, depth = 0;
+  keys_and_span(cur, m, depth);
+  for (;;) {
+    auto host = meta.cpu();  // waits for the kernels
+    const int64_t* mp = host.data_ptr<int64_t>();
+    const uint32_t status = (uint32_t)mp[RANK_M_STATUS];
+    TORCH_CHECK(!(status & RANK_BAD_DICT), fn, ": offs does not ascend from "
+                "0 within the ", bytes, " bytes of blob");
+    if (status & RANK_DUPLICATE) return std::make_tuple(rank, true);
+    if (cur >= 0) {
+      m = mp[RANK_M_COUNT];
+      if (m == 0) break;
+      if (mp[RANK_M_MAXRUN] <= finish_max) {
+        launch("rank_finish", rank_finish_kernel, blocks(m), dim3(RANK_BLOCK),
+               0, words, (long long)bytes, offs_p,
+               (const uint32_t*)u32(act[cur]), (const uint32_t*)u32(grp[cur]),
+               (const uint32_t*)u32(gstart[cur]), (uint32_t)m,
+               (long long)depth, (long long*)rank.data_ptr(), meta_p);
+        const auto last = meta.cpu();  // waits for the finish
+        return std::make_tuple(
+            rank, (last.data_ptr<int64_t>()[RANK_M_STATUS] &
+                   RANK_DUPLICATE) != 0);
+      }
+    }
+    const int64_t m8 = (m + 1 + 7) / 8 * 8;
+    const int64_t round_sums =
+        (2 * m8 + SORT_SCAN_TILE - 1) / SORT_SCAN_TILE;
+    auto perm = m >= 2
+        ? sort_passes((const long long*)rows_p, m, 2,
+                      meta_p + RANK_M_SPAN,
+                      (const unsigned long long*)(mp + RANK_M_SPAN), dev)
+        : torch::zeros({1}, i32);
+    const int nxt = cur < 0 ? 0 : cur ^ 1;
+    const uint32_t* act_p = cur < 0 ? nullptr : u32(act[cur]);
+    const uint32_t* grp_p = cur < 0 ? nullptr : u32(grp[cur]);
+    const uint32_t* gstart_p = cur < 0 ? nullptr : u32(gstart[cur]);
+    launch("rank_bound", rank_bound_kernel, blocks(m8), dim3(RANK_BLOCK), 0,
+           (const longlong2*)rows_p, (const uint32_t*)perm.data_ptr(), act_p,
+           (uint32_t)m, (uint32_t)m8, scan_p, sid_p, meta_p);
+    launch("sort_scan", sort_scan_kernel, dim3((uint32_t)round_sums),
+           dim3(SORT_BLOCK), 0, scan_p, (uint32_t)(2 * m8), sums_p);
+    launch("sort_scan_sums", sort_scan_sums_kernel, dim3(1), dim3(SORT_BLOCK),
+           0, sums_p, (uint32_t)round_sums);
+    launch("rank_heads", rank_heads_kernel, blocks(m), dim3(RANK_BLOCK), 0,
+           (const uint32_t*)scan_p, (const uint32_t*)sums_p, (uint32_t)m,
+           head_p);
+    launch("rank_assign", rank_assign_kernel, blocks(m), dim3(RANK_BLOCK), 0,
+           (const uint32_t*)scan_p, (const uint32_t*)sums_p,
+           (const uint32_t*)head_p, (const uint32_t*)sid_p, grp_p, gstart_p,
+           (uint32_t)m, (uint32_t)m8, (long long*)rank.data_ptr(),
+           u32(act[nxt]), u32(grp[nxt]), u32(gstart[nxt]), meta_p);
+    cur = nxt;
+    depth += RANK_CHUNK;
+    keys_and_span(cur, m, depth);
+  }
+  return std::make_tuple(rank, false);
 }
 
 }  // namespace dn

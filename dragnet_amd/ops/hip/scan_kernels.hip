@@ -24,7 +24,8 @@
 // unify_strings.h (device only: one dictionary out of the ranks'),
 // partition_rows.h (device only: the rows of a rank split by destination),
 // encode_table.h (device only: a scan's tables to the merge's wire form),
-// render_points.h (device only: the merged rows as NDJSON point lines).
+// render_points.h (device only: the merged rows as NDJSON point lines),
+// rank_strings.h (kernels device only: the dictionary's byte-order ranks).
 
 #include "common.h"
 #include <hip/hip_runtime.h>
@@ -617,5 +618,8 @@ __global__ void extract_numdict_kernel(NumDict D, double* out_vals,
 
 // the merged rows as the point lines `dn scan --points` prints; last again
 #include "render_points.h"
+
+// the rank of every dictionary string in byte order; last again
+#include "rank_strings.h"
 
 }  // extern "C++"
