@@ -37,6 +37,12 @@ and hands the gathered tensors to reaggregate().
      dictionary string in byte order: one sorted() over the bytes on the
      host, or the rank_strings kernels (ops/hip/rank_strings.h) on the
      dictionary where it lies; DRAGNET_RANK_GPU chooses.
+  parse_points / reduce_points: the reduce side.  Tagged NDJSON point
+     lines (dn index-read's input) to rows by the parse_points kernels
+     (ops/hip/parse_points.h), their string elements spans into the
+     uploaded text, which unify_strings and merge_rows take as they are;
+     what the device punts stays with the C++ reducer
+     (points.reduce_tagged_stream; DRAGNET_PARSE_GPU chooses).
   DRAGNET_UNIFY_GPU, DRAGNET_MERGE_GPU and DRAGNET_PARTITION_GPU choose
   (_use_gpu); the host and device paths give the same bits.
 """
@@ -783,3 +789,163 @@ def reaggregate_points(query, parts, strings_per_part, device=None):
     gstrings, remaps = _unify(strings_per_part, device, as_blob=True)
     uniq, sums = _group_rows(parts, remaps, nk, device, keep=True)
     return render_points(query, uniq, sums, gstrings, device)
+
+
+# ---- the reduce side: point lines back to rows ----------------------------
+
+# caps of ops/hip/parse_points.h; beyond them the op is not called
+_PARSE_MAX_METRICS = 8
+_PARSE_MAX_KEY = 8
+_PARSE_NAME_BYTES = 2048
+_PARSE_TAIL = b"undefined"
+PARSE_SKIP, PARSE_DROP, PARSE_TAKEN, PARSE_PUNT = 0, 1, 2, 3
+
+
+def _parse_specs(queries):
+    """The metrics' columns as ops.parse_points takes them, (ncols,
+    kinds, steps, names, name_offs), or None where its caps do not hold:
+    too many metrics or columns, too many name bytes, or an lquantize
+    step that is zero or not a double (the device divides doubles)."""
+    from .points import fast_reduce_spec
+    if not 1 <= len(queries) <= _PARSE_MAX_METRICS:
+        return None
+    ncols, kinds, steps, names = [], [], [], []
+    for q in queries:
+        spec = fast_reduce_spec(q)
+        if len(spec) > _PARSE_MAX_KEY:
+            return None
+        ncols.append(len(spec))
+        for name, kind, step in spec:
+            if kind == 3:
+                exact = q.bucketizers[name].step
+                if exact == 0 or step != exact:
+                    return None
+            try:
+                names.append(name.encode("utf-8"))
+            except UnicodeEncodeError:
+                return None
+            kinds.append(kind)
+            steps.append(step)
+    offs = [0]
+    for n in names:
+        offs.append(offs[-1] + len(n))
+    if offs[-1] > _PARSE_NAME_BYTES:
+        return None
+    return ncols, kinds, steps, b"".join(names), offs
+
+
+_parse_pinned = None  # the upload's staging buffer, grown as needed
+
+
+def _parse_upload(data, device):
+    """`data` and the tail as one uint8 tensor on the device, through a
+    pinned host buffer that is kept between calls (a 64 MiB chunk per
+    call is the stream's rhythm).  The copy has landed on return."""
+    global _parse_pinned
+    import torch
+    n = len(data) + len(_PARSE_TAIL)
+    if _parse_pinned is None or _parse_pinned.numel() < n:
+        _parse_pinned = torch.empty(max(n, 1 << 16), dtype=torch.uint8,
+                                    pin_memory=True)
+    stage = _parse_pinned.numpy()
+    stage[:len(data)] = np.frombuffer(data, dtype=np.uint8)
+    stage[len(data):n] = np.frombuffer(_PARSE_TAIL, dtype=np.uint8)
+    return _parse_pinned[:n].to(device)
+
+
+def parse_points(data, queries, device=None):
+    """The parse_points kernels (ops/hip/parse_points.h) over `data`,
+    tagged NDJSON point lines as `dn index-scan` writes them: uploads
+    the bytes with the constant `undefined` behind them and returns
+    (tables, counters, punted, classes), or None where the op's caps do
+    not hold (_parse_specs; 2^31 bytes).  tables: per metric a WireTable
+    of the taken lines in line order, on the device, whose dictionary
+    is the span form (text, start, length): a string element indexes
+    the spans, which point into the uploaded text, one numbering for
+    all metrics.  counters: int64 [M, 2] on the host, ninputs and
+    nonnumeric.  punted: the lines left to the host reducer, as bytes.
+    classes: uint8 per line on the device (PARSE_*)."""
+    from .ops import load_ops
+    ops = load_ops(required=True)  # a missing extension is an error
+    specs = _parse_specs(queries)
+    if specs is None or len(data) >= (1 << 31) - len(_PARSE_TAIL):
+        return None
+    device, _up = _work_device(device, [])
+    text = _parse_upload(data, device)
+    (metric, rows, span_start, span_len, vals, counters, punts,
+     classes) = ops.parse_points(text, len(data), *specs)
+    counters = counters.cpu().numpy()
+    kmax = rows.shape[1] - 1
+    tables = []
+    for m, nk in enumerate(specs[0]):
+        if len(specs[0]) == 1:
+            mine, mvals = rows, vals
+        else:
+            mask = metric == m
+            mine, mvals = rows[mask], vals[mask]
+        tables.append(WireTable(
+            mine[:, :nk], mine[:, kmax], mvals,
+            (text, span_start, span_len),
+            int(counters[m, 0]), int(counters[m, 1])))
+    punted = [bytes(data[a:b]) for a, b in punts.cpu().tolist()]
+    return tables, counters, punted, classes
+
+
+def reduce_points(data, aggs, queries, device=None):
+    """One chunk of a tagged point stream into `aggs`, on the device:
+    parse_points, one unify_strings call over all spans, merge_rows per
+    metric with the remap in place (a metric without breakdowns is an
+    int64 sum), _decode_rows over the distinct rows with only the
+    distinct strings decoded, and the result added into aggs exactly as
+    points.reduce_tagged_stream's run() does.  Returns the punted lines,
+    for the host reducer; None, with nothing committed, where the op's
+    caps do not hold or merge_rows reports sums that are not exact (a
+    sum at or beyond 2^53): the whole chunk is the host reducer's."""
+    import torch
+
+    from .ops import load_ops
+    ops = load_ops(required=True)  # a missing extension is an error
+    parsed = parse_points(data, queries, device)
+    if parsed is None:
+        return None
+    tables, _counters, punted, _classes = parsed
+    text, span_start, span_len = tables[0].strings
+    strings, remap = [], None
+    if span_start.numel():
+        remap, first = ops.unify_strings(text, span_start, span_len)
+        end = len(data)  # the distinct strings, from the host's copy
+        strings = [
+            (data[a:a + n] if a < end else _PARSE_TAIL).decode("utf-8")
+            for a, n in zip(span_start[first].cpu().tolist(),
+                            span_len[first].cpu().tolist())]
+    else:
+        remap = torch.zeros(0, dtype=torch.int64, device=text.device)
+    merged = []
+    for q, wt in zip(queries, tables):
+        nk = len(q.breakdowns)
+        n = int(wt.vals.shape[0])
+        if n == 0:
+            merged.append(None)
+        elif nk == 0:
+            # below 2^62 the f64 total tells that the int64 one is exact
+            if float(wt.vals.sum()) >= 2.0 ** 62:
+                return None
+            merged.append({(): int(wt.vals.to(torch.int64).sum())})
+        else:
+            rows = torch.cat([wt.codes, wt.tagpack.reshape(-1, 1)],
+                             dim=1).contiguous()
+            uniq, sums, exact = ops.merge_rows(
+                rows, wt.vals.contiguous(), nk,
+                seg_start=torch.tensor([0, n]), remap=remap,
+                remap_off=torch.tensor([0, int(remap.numel())]))
+            if not exact:
+                return None
+            merged.append(_decode_rows(q, uniq.cpu().numpy(),
+                                       sums.cpu().numpy(), strings).table)
+    for agg, wt, t in zip(aggs, tables, merged):
+        agg.ninputs += wt.ninputs
+        agg.ndropped_nonnumeric += wt.ndropped_nonnumeric
+        tab = agg.table
+        for k, v in (t or {}).items():
+            tab[k] = tab.get(k, 0) + v
+    return punted

@@ -111,7 +111,7 @@ ScanKernel xpose_kernel(int mw, int xg) {
 }  // namespace dn
 
 // sort_rows, merge_rows, unify_strings, partition_rows, encode_table,
-// render_points, rank_strings
+// render_points, rank_strings, parse_points
 #include "ext_merge.h"
 
 namespace dn {
@@ -758,6 +758,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("finish_max") = (int)dn::RANK_FINISH_MAX,
         "rank of every string of a wire-form dictionary in byte order -> "
         "(rank int64 [G], duplicate)");
+  m.def("parse_points", &dn::parse_points, py::arg("text"),
+        py::arg("data_len"), py::arg("ncols"), py::arg("kinds"),
+        py::arg("steps"), py::arg("names"), py::arg("name_offs"),
+        "tagged NDJSON point lines to rows -> (metric, rows [t, kmax + 1], "
+        "span_start, span_len, vals, counters [M, 2], punts [p, 2], cls)");
   m.def("lds_bytes", &dn::lds_bytes, py::arg("nf"), py::arg("nm"),
         py::arg("ns") = 0, py::arg("columnar") = false,
         "dynamic LDS bytes of a scan / columnar launch (host only)");
@@ -800,4 +805,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("ENC_STAGE_BYTES") = (int)dn::ENC_STAGE_BYTES;
   m.attr("RANK_FINISH_MAX") = (int)dn::RANK_FINISH_MAX;
   m.attr("MAX_FIELDS") = (int)dn::MAX_FIELDS;
+  m.attr("PP_MAX_METRICS") = (int)dn::PP_MAX_METRICS;
+  m.attr("PP_NAME_BYTES") = (int)dn::PP_NAME_BYTES;
+  m.attr("PP_MAX_LINE") = (int)dn::PP_MAX_LINE;
+  m.attr("PP_STAGE_BYTES") = (int)dn::PP_STAGE_BYTES;
 }

@@ -2,8 +2,8 @@
 // (dragnet_amd/merge.py): sort_rows (sort_rows.h), merge_rows
 // (merge_rows.h), unify_strings (unify_strings.h), partition_rows
 // (partition_rows.h), encode_table (encode_table.h), render_points
-// (render_points.h) and rank_strings (rank_strings.h), free functions that
-// keep nothing between calls.
+// (render_points.h), rank_strings (rank_strings.h) and parse_points
+// (parse_points.h), free functions that keep nothing between calls.
 // Part of ext.hip's translation unit, behind its launch plumbing (launch,
 // on_dev, allocating, GRID_CAP).
 #pragma once
@@ -940,6 +940,173 @@ std::tuple<torch::Tensor, bool> rank_strings(torch::Tensor blob,
     keys_and_span(cur, m, depth);
   }
   return std::make_tuple(rank, false);
+}
+
+// Tagged point lines to rows (parse_points.h): text uint8 [data_len + 9],
+// the NDJSON data and directly behind it the bytes `undefined`; the
+// metrics' columns as points.fast_reduce_spec gives them, flattened:
+// ncols per metric, then kinds (0 plain, 1 date, 2 quantize, 3 lquantize),
+// steps and names over all columns in order, the names as one byte string
+// with name_offs [columns + 1].  Returns (metric int32 [t], rows int64
+// [t, kmax + 1], span_start int64 [s], span_len int64 [s], vals f64 [t],
+// counters int64 [M, 2], punts int64 [p, 2], cls uint8 [lines]): the taken
+// lines in line order, kmax the largest column count (unused columns 0,
+// the last word the tag pack), a STR element an index into the spans,
+// which point into text; per metric ninputs and nonnumeric; the stripped
+// byte range of every punted line; the class of every line.  Syncs twice:
+// for the line count, and for the three totals that size the outputs.
+// An empty text launches nothing.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
+           torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
+parse_points(torch::Tensor text, int64_t data_len,
+             std::vector<int64_t> ncols, std::vector<int64_t> kinds,
+             std::vector<double> steps, std::string names,
+             std::vector<int64_t> name_offs) {
+  const char* fn = "parse_points";
+  const auto dev = text.device();
+  check_arg(fn, "text", text, torch::kUInt8, 1, dev);
+  TORCH_CHECK(data_len >= 0 && data_len < ((int64_t)1 << 31) &&
+                  text.numel() == data_len + (int64_t)PP_TAIL,
+              fn, ": text must hold data_len < 2^31 bytes and the ",
+              PP_TAIL, " bytes `undefined` behind them");
+  const int64_t M = (int64_t)ncols.size();
+  TORCH_CHECK(M >= 1 && M <= PP_MAX_METRICS, fn, ": 1..",
+              (int)PP_MAX_METRICS, " metrics");
+  const int64_t C = (int64_t)kinds.size();
+  TORCH_CHECK((int64_t)steps.size() == C && (int64_t)name_offs.size() == C + 1,
+              fn, ": kinds, steps and name_offs (+ 1) differ in length");
+  TORCH_CHECK(name_offs[0] == 0 && name_offs[C] == (int64_t)names.size() &&
+                  names.size() <= (size_t)PP_NAME_BYTES,
+              fn, ": name_offs must run from 0 to the ", names.size(),
+              " bytes of names, at most ", (int)PP_NAME_BYTES);
+  PpSpecs P;
+  memset(&P, 0, sizeof(P));
+  P.nm = (int32_t)M;
+  memcpy(P.names, names.data(), names.size());
+  int kmax = 0;
+  int64_t c = 0;
+  for (int64_t m = 0; m < M; m++) {
+    TORCH_CHECK(ncols[m] >= 0 && ncols[m] <= MAX_KEY && c + ncols[m] <= C, fn,
+                ": a metric has 0..", (int)MAX_KEY, " columns");
+    P.nk[m] = (uint8_t)ncols[m];
+    kmax = std::max(kmax, (int)ncols[m]);
+    for (int64_t j = 0; j < ncols[m]; j++, c++) {
+      TORCH_CHECK(kinds[c] >= PP_COL_PLAIN && kinds[c] <= PP_COL_LQUANTIZE &&
+                      name_offs[c] <= name_offs[c + 1],
+                  fn, ": a column kind is 0..3 and name_offs ascends");
+      P.kind[m][j] = (uint8_t)kinds[c];
+      P.step[m][j] = steps[c];
+      P.name_off[m][j] = (uint16_t)name_offs[c];
+      P.name_len[m][j] = (uint16_t)(name_offs[c + 1] - name_offs[c]);
+    }
+  }
+  TORCH_CHECK(c == C, fn, ": ncols sums to ", c, ", kinds has ", C);
+
+  const auto u8 = on_dev(dev, torch::kUInt8);
+  const auto i32 = on_dev(dev, torch::kInt32);
+  const auto i64 = on_dev(dev, torch::kInt64);
+  const auto f64 = on_dev(dev, torch::kFloat64);
+  auto result = [&](int64_t t, int64_t s, int64_t p, torch::Tensor counters,
+                    torch::Tensor cls) {
+    return std::make_tuple(
+        torch::empty({t}, i32), torch::empty({t, (int64_t)kmax + 1}, i64),
+        torch::empty({s}, i64), torch::empty({s}, i64), torch::empty({t}, f64),
+        counters, torch::empty({p, 2}, i64), cls);
+  };
+  if (data_len == 0)
+    return result(0, 0, 0, torch::zeros({M, 2}, i64), torch::empty({0}, u8));
+
+  c10::DeviceGuard guard(dev);
+  // 16-byte loads from the base of text
+  if ((uintptr_t)text.data_ptr() % 16 != 0) text = text.clone();
+
+  PpArgs A = {};
+  const int64_t nseg = (data_len + PP_NL_SEG - 1) / PP_NL_SEG;
+  const int64_t seg8 = (nseg + 1 + 7) / 8 * 8;
+  const int64_t seg_nsums = (seg8 + SORT_SCAN_TILE - 1) / SORT_SCAN_TILE;
+  torch::Tensor specs, seg_scan, seg_sums, meta, counters;
+  allocating([&] {
+    specs = torch::from_blob(&P, {(int64_t)sizeof(P)}, torch::kUInt8).to(dev);
+    seg_scan = torch::zeros({seg8}, i32);
+    seg_sums = torch::empty({seg_nsums}, i32);
+    meta = torch::zeros({PP_M_WORDS}, i64);
+    counters = torch::zeros({M, 2}, i64);
+  }, "cannot allocate the line index (", seg8, " segments)");
+  A.text = (const uint8_t*)text.data_ptr();
+  A.data_len = (uint32_t)data_len;
+  A.specs = (const PpSpecs*)specs.data_ptr();
+  A.kmax = kmax;
+  A.nseg = (uint32_t)nseg;
+  A.seg_scan = (uint32_t*)seg_scan.data_ptr();
+  A.seg_sums = (uint32_t*)seg_sums.data_ptr();
+  A.meta = (unsigned long long*)meta.data_ptr();
+  A.counters = (unsigned long long*)counters.data_ptr();
+
+  const dim3 seg_grid((uint32_t)((nseg + 3) / 4));
+  launch("parse_nl_count", parse_nl_count_kernel, seg_grid, dim3(PP_BLOCK), 0,
+         A);
+  launch("sort_scan", sort_scan_kernel, dim3((uint32_t)seg_nsums),
+         dim3(SORT_BLOCK), 0, A.seg_scan, (uint32_t)seg8, A.seg_sums);
+  launch("sort_scan_sums", sort_scan_sums_kernel, dim3(1), dim3(SORT_BLOCK), 0,
+         A.seg_sums, (uint32_t)seg_nsums);
+  launch("parse_lines", parse_lines_kernel, dim3(1), dim3(64), 0, A);
+  auto host = meta.cpu();  // waits for the kernels
+  const int64_t n_nl = host.data_ptr<int64_t>()[PP_M_NL];
+  const int64_t n_lines = host.data_ptr<int64_t>()[PP_M_LINES];
+
+  const int64_t n8 = (n_lines + 1 + 7) / 8 * 8;
+  const int64_t nsums = (3 * n8 + SORT_SCAN_TILE - 1) / SORT_SCAN_TILE;
+  torch::Tensor nl_pos, cls, scan, sums;
+  allocating([&] {
+    nl_pos = torch::empty({n_nl}, i32);
+    cls = torch::empty({n_lines}, u8);
+    scan = torch::zeros({3 * n8}, i32);
+    sums = torch::empty({nsums}, i32);
+  }, "cannot allocate the line buffers (", n_lines, " lines)");
+  A.n_nl = (uint32_t)n_nl;
+  A.n_lines = (uint32_t)n_lines;
+  A.nl_pos = (uint32_t*)nl_pos.data_ptr();
+  A.cls = (uint8_t*)cls.data_ptr();
+  A.n8 = (uint32_t)n8;
+  A.scan = (uint32_t*)scan.data_ptr();
+  A.sums = (uint32_t*)sums.data_ptr();
+  const dim3 line_grid((uint32_t)((n_lines + PP_BLOCK - 1) / PP_BLOCK));
+  if (n_nl > 0)
+    launch("parse_nl_write", parse_nl_write_kernel, seg_grid, dim3(PP_BLOCK),
+           0, A);
+  launch("parse_measure", parse_measure_kernel, line_grid, dim3(PP_BLOCK), 0,
+         A);
+  launch("parse_measure_global", parse_measure_global_kernel, line_grid,
+         dim3(PP_BLOCK), 0, A);
+  launch("sort_scan", sort_scan_kernel, dim3((uint32_t)nsums),
+         dim3(SORT_BLOCK), 0, A.scan, (uint32_t)(3 * n8), A.sums);
+  launch("sort_scan_sums", sort_scan_sums_kernel, dim3(1), dim3(SORT_BLOCK), 0,
+         A.sums, (uint32_t)nsums);
+  launch("parse_totals", parse_totals_kernel, dim3(1), dim3(64), 0, A);
+  host = meta.cpu();  // waits for the kernels
+  const int64_t* mp = host.data_ptr<int64_t>();
+  decltype(result(0, 0, 0, counters, cls)) out;
+  allocating([&] {
+    out = result(mp[PP_M_TAKEN], mp[PP_M_SPANS], mp[PP_M_PUNTS], counters,
+                 cls);
+  }, "cannot allocate the parsed rows (", mp[PP_M_TAKEN], " rows, ",
+     mp[PP_M_SPANS], " spans)");
+  A.n_taken = (uint32_t)mp[PP_M_TAKEN];
+  A.n_spans = (uint32_t)mp[PP_M_SPANS];
+  A.n_punts = (uint32_t)mp[PP_M_PUNTS];
+  A.metric = (int*)std::get<0>(out).data_ptr();
+  A.rows = (long long*)std::get<1>(out).data_ptr();
+  A.span_start = (long long*)std::get<2>(out).data_ptr();
+  A.span_len = (long long*)std::get<3>(out).data_ptr();
+  A.vals = (double*)std::get<4>(out).data_ptr();
+  A.punts = (long long*)std::get<6>(out).data_ptr();
+  if (A.n_taken || A.n_punts) {
+    launch("parse_emit", parse_emit_kernel, line_grid, dim3(PP_BLOCK), 0, A);
+    if (mp[PP_M_WIDE])  // some tile did not fit the stage
+      launch("parse_emit_global", parse_emit_global_kernel, line_grid,
+             dim3(PP_BLOCK), 0, A);
+  }
+  return out;
 }
 
 }  // namespace dn

@@ -25,7 +25,8 @@
 // partition_rows.h (device only: the rows of a rank split by destination),
 // encode_table.h (device only: a scan's tables to the merge's wire form),
 // render_points.h (device only: the merged rows as NDJSON point lines),
-// rank_strings.h (kernels device only: the dictionary's byte-order ranks).
+// rank_strings.h (kernels device only: the dictionary's byte-order ranks),
+// parse_points.h (kernels device only: tagged point lines back to rows).
 
 #include "common.h"
 #include <hip/hip_runtime.h>
@@ -621,5 +622,8 @@ __global__ void extract_numdict_kernel(NumDict D, double* out_vals,
 
 // the rank of every dictionary string in byte order; last again
 #include "rank_strings.h"
+
+// tagged point lines back to the rows the merge groups; last again
+#include "parse_points.h"
 
 }  // extern "C++"

@@ -257,7 +257,11 @@ def reduce_tagged_stream(stream, aggs, queries):
     """Drain a tagged-point NDJSON stream through the C++ reducer,
     merging fast-path groups into each Aggregator and returning the
     punted lines (anything outside the flat-scalar fast shape) for
-    the caller's per-line Python path.  Raises ImportError when the
+    the caller's per-line Python path.  Per chunk, DRAGNET_PARSE_GPU and
+    DRAGNET_PARSE_GPU_BYTES (merge._use_gpu; infinity by default:
+    profiles/r16_parse_points.md) send it through merge.reduce_points
+    first, the parse_points kernels, and only what those punt through
+    the C++ reducer.  Raises ImportError when the
     native extension is unavailable (caller falls back wholesale)."""
     import os
     if os.environ.get("DRAGNET_PY_POINTS") == "1":
@@ -267,7 +271,23 @@ def reduce_tagged_stream(stream, aggs, queries):
     specs = [fast_reduce_spec(q) for q in queries]
     punted_all = []
 
+    # merge is imported only where _use_gpu could choose the device: mode
+    # "1", or a threshold beside any mode but "0"
+    mode = os.environ.get("DRAGNET_PARSE_GPU", "auto")
+    may_gpu = mode == "1" or (
+        mode != "0" and "DRAGNET_PARSE_GPU_BYTES" in os.environ)
+
     def run(data):
+        if may_gpu:
+            from .merge import _use_gpu, reduce_points
+            left = None
+            if _use_gpu("DRAGNET_PARSE_GPU", "DRAGNET_PARSE_GPU_BYTES",
+                        len(data)):
+                left = reduce_points(data, aggs, queries)
+            if left is not None:  # else the chunk is the host's, whole
+                if not left:
+                    return
+                data = b"\n".join(left) + b"\n"
         tables, nin, nonn, punted = _points.reduce_tagged(data, specs)
         for agg, t, n, d in zip(aggs, tables, nin, nonn):
             agg.ninputs += n
