@@ -15,6 +15,10 @@ and hands the gathered tensors to reaggregate().
      scan's extraction snapshot to it on the device, where it lies: the
      encode_table kernels (ops/hip/encode_table.h); a WireTable either
      way.  DRAGNET_ENCODE_GPU chooses (encode_on_gpu).
+  format_numbers: the key strings of the fractional and large numbers
+     that export hands back, plan.number_key per value on the host or the
+     format_numbers kernels (ops/hip/format_numbers.h) on the device;
+     DRAGNET_FORMAT_GPU chooses.
   C2 unify_dictionaries: the global dictionary, first seen first in rank
      order, and per rank the table from its codes to global ones:
      FirstSeen on the host, or the unify_strings kernels
@@ -151,12 +155,13 @@ def _encode_device(snap, metric, query):
     raises there).  The device renders plain strings, integral numbers
     and the constants; the E exceptions it hands back (escaped or
     ill-formed strings, array texts, other numbers) are rendered here,
-    once per distinct value, by the host path's own functions, and
-    appended to the dictionary in the order their codes assume."""
+    once per distinct value, and appended to the dictionary in the order
+    their codes assume: strings and array texts by the host path's own
+    functions, the numbers by format_numbers."""
     import torch
 
     from .engine.decode import decode_json_string
-    from .engine.plan import array_key, number_key
+    from .engine.plan import array_key
     from .ops import load_ops
     ops = load_ops(required=True)  # a missing extension is an error
     keys, counts, n = snap["aggs"][metric]
@@ -168,23 +173,56 @@ def _encode_device(snap, metric, query):
     if refused:
         return None
     if exc_kind.numel():
-        raw = exc_blob.cpu().numpy().tobytes()
-        at = exc_offs.cpu().tolist()
+        # ordered by (kind, id): strings and array texts, then the numbers
+        kinds = exc_kind.cpu().tolist()
+        head = len(kinds) - kinds.count(2)
+        at = exc_offs[:head + 1].cpu().tolist()
+        raw = exc_blob[:at[head]].cpu().numpy().tobytes()
         extra = []
-        for kind, a, b in zip(exc_kind.cpu().tolist(), at, at[1:]):
-            if kind == 2:
-                s = number_key(np.frombuffer(raw[a:b], np.float64)[0])
-            else:
-                s = decode_json_string(raw[a:b])
-                if kind == 1:
-                    s = array_key(s)
+        for kind, a, b in zip(kinds, at, at[1:]):
+            s = decode_json_string(raw[a:b])
+            if kind == 1:
+                s = array_key(s)
             extra.append(s.encode("utf-8"))
+        # the tail is 8 bytes a number; format_numbers keeps it on the
+        # device where DRAGNET_FORMAT_GPU says so
+        nums = exc_blob[at[head]:].clone().view(torch.float64)
+        num_blob, num_offs = format_numbers(nums, blob.device)
         ends = np.cumsum([len(e) for e in extra]).astype(np.int64)
-        blob = torch.cat([blob, torch.from_numpy(np.frombuffer(
-            b"".join(extra), dtype=np.uint8).copy()).to(blob.device)])
-        offs = torch.cat([offs,
-                          offs[-1] + torch.from_numpy(ends).to(offs.device)])
+        dev = blob.device
+        parts = [blob, torch.from_numpy(np.frombuffer(
+            b"".join(extra), dtype=np.uint8).copy()).to(dev),
+            torch.as_tensor(num_blob).to(dev)]
+        mid = offs[-1] + (int(ends[-1]) if head else 0)
+        offs = torch.cat([offs, offs[-1] + torch.from_numpy(ends).to(dev),
+                          mid + torch.as_tensor(num_offs).to(dev)[1:]])
+        blob = torch.cat(parts)
     return codes, tagpack, vals, (blob, offs)
+
+
+def format_numbers(values, device=None):
+    """The key strings of numbers in a plain column, JS String(number),
+    as a dictionary in wire form: (blob uint8, offs int64 [n + 1]) for
+    f64 `values`, numpy or torch on any device.  On the host it is
+    plan.number_key per value and _strings_blob (numpy out), which is
+    the definition; on the GPU the format_numbers kernels
+    (ops/hip/format_numbers.h) give the same bytes and nothing leaves
+    the device.  DRAGNET_FORMAT_GPU and DRAGNET_FORMAT_GPU_NUMBERS
+    numbers choose (_use_gpu; infinity by default:
+    profiles/r17_format_numbers.md)."""
+    n = int(np.prod(values.shape))
+    if _use_gpu("DRAGNET_FORMAT_GPU", "DRAGNET_FORMAT_GPU_NUMBERS", n):
+        import torch
+
+        from .ops import load_ops
+        ops = load_ops(required=True)  # a missing extension is an error
+        device, up = _work_device(device, [values])
+        return ops.format_numbers(
+            up(values, torch.float64).reshape(-1).contiguous())
+    from .engine.plan import number_key
+    blob, offs = _strings_blob(
+        [number_key(v) for v in _np(values).reshape(-1).astype(np.float64)])
+    return np.frombuffer(blob, dtype=np.uint8).copy(), offs
 
 
 def encode_table(source, query, metric=0):

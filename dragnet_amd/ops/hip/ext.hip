@@ -111,7 +111,7 @@ ScanKernel xpose_kernel(int mw, int xg) {
 }  // namespace dn
 
 // sort_rows, merge_rows, unify_strings, partition_rows, encode_table,
-// render_points, rank_strings, parse_points
+// render_points, rank_strings, format_numbers, parse_points
 #include "ext_merge.h"
 
 namespace dn {
@@ -758,6 +758,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("finish_max") = (int)dn::RANK_FINISH_MAX,
         "rank of every string of a wire-form dictionary in byte order -> "
         "(rank int64 [G], duplicate)");
+  m.def("format_numbers", &dn::format_numbers, py::arg("x"),
+        py::arg("variant") = 0,
+        "JavaScript strings of f64 values -> (text uint8, offs int64 "
+        "[n + 1])");
   m.def("parse_points", &dn::parse_points, py::arg("text"),
         py::arg("data_len"), py::arg("ncols"), py::arg("kinds"),
         py::arg("steps"), py::arg("names"), py::arg("name_offs"),

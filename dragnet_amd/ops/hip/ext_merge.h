@@ -2,8 +2,9 @@
 // (dragnet_amd/merge.py): sort_rows (sort_rows.h), merge_rows
 // (merge_rows.h), unify_strings (unify_strings.h), partition_rows
 // (partition_rows.h), encode_table (encode_table.h), render_points
-// (render_points.h), rank_strings (rank_strings.h) and parse_points
-// (parse_points.h), free functions that keep nothing between calls.
+// (render_points.h), rank_strings (rank_strings.h), format_numbers
+// (format_numbers.h) and parse_points (parse_points.h), free functions
+// that keep nothing between calls.
 // Part of ext.hip's translation unit, behind its launch plumbing (launch,
 // on_dev, allocating, GRID_CAP).
 #pragma once
@@ -940,6 +941,78 @@ std::tuple<torch::Tensor, bool> rank_strings(torch::Tensor blob,
     keys_and_span(cur, m, depth);
   }
   return std::make_tuple(rank, false);
+}
+
+// The JavaScript strings of f64 values (format_numbers.h): x f64 [n].
+// Returns (text uint8 [bytes], offs int64 [n + 1]): string i is
+// text[offs[i] : offs[i + 1]], ECMAScript Number::toString of x[i], what
+// plan.number_key gives.  variant is for measurements (FMT_RECOMPUTE = 1:
+// convert in both passes and park nothing; FMT_LDS_TABLE = 2: the power
+// table staged in LDS); 0 is what runs.  n == 0 launches nothing.  Syncs
+// once, after the measuring kernels, to read the byte total; the emit
+// kernel is enqueued behind that.
+std::tuple<torch::Tensor, torch::Tensor> format_numbers(torch::Tensor x,
+                                                        int64_t variant) {
+  const char* fn = "format_numbers";
+  const auto dev = x.device();
+  check_arg(fn, "x", x, torch::kFloat64, 1, dev);
+  const int64_t n = x.size(0);
+  TORCH_CHECK(n < ((int64_t)1 << 31) - 16, fn, ": more than 2^31 numbers");
+  TORCH_CHECK(variant >= 0 && variant <= 3, fn, ": variant is 0..3");
+  const auto u8 = on_dev(dev, torch::kUInt8);
+  const auto i32 = on_dev(dev, torch::kInt32);
+  const auto i64 = on_dev(dev, torch::kInt64);
+  if (n == 0)
+    return std::make_tuple(torch::empty({0}, u8), torch::zeros({1}, i64));
+
+  c10::DeviceGuard guard(dev);
+  const bool parked = !(variant & FMT_RECOMPUTE);
+  const int64_t n8 = (n + 1 + 7) / 8 * 8;
+  const int64_t nsums = (n8 + SORT_SCAN_TILE - 1) / SORT_SCAN_TILE;
+  torch::Tensor dig, form, len_scan, len_sums, base, meta;
+  allocating([&] {
+    dig = torch::empty({parked ? n : 0}, i64);
+    form = torch::empty({parked ? n : 0}, i32);
+    len_scan = torch::zeros({n8}, i32);
+    len_sums = torch::empty({nsums}, i32);
+    base = torch::empty({nsums}, i64);
+    meta = torch::zeros({1}, i64);
+  }, "cannot allocate the format buffers (", n, " numbers)");
+  FmtArgs A = {};
+  A.x = (const double*)x.data_ptr();
+  A.n = (uint32_t)n;
+  A.dig = (unsigned long long*)dig.data_ptr();
+  A.form = (uint32_t*)form.data_ptr();
+  A.len_scan = (uint32_t*)len_scan.data_ptr();
+  A.len_sums = (uint32_t*)len_sums.data_ptr();
+  A.nsums = (uint32_t)nsums;
+  A.base = (long long*)base.data_ptr();
+  A.meta = (unsigned long long*)meta.data_ptr();
+
+  using Kernel = void (*)(FmtArgs);
+  static const Kernel measure[4] = {
+      format_measure_kernel<0>, format_measure_kernel<1>,
+      format_measure_kernel<2>, format_measure_kernel<3>};
+  static const Kernel emit[4] = {
+      format_emit_kernel<0>, format_emit_kernel<1>, format_emit_kernel<2>,
+      format_emit_kernel<3>};
+  const dim3 grid((uint32_t)((n + FMT_BLOCK - 1) / FMT_BLOCK));
+  launch("format_measure", measure[variant], grid, dim3(FMT_BLOCK), 0, A);
+  launch("sort_scan", sort_scan_kernel, dim3((uint32_t)nsums),
+         dim3(SORT_BLOCK), 0, A.len_scan, (uint32_t)n8, A.len_sums);
+  launch("format_totals", format_totals_kernel, dim3(1), dim3(SORT_BLOCK), 0,
+         A);
+  const int64_t bytes = meta.cpu().data_ptr<int64_t>()[0];  // waits
+  torch::Tensor text, offs;
+  allocating([&] {
+    text = torch::empty({bytes}, u8);
+    offs = torch::empty({n + 1}, i64);
+  }, "cannot allocate the number strings (", bytes, " bytes for ", n,
+     " numbers)");
+  A.text = (uint8_t*)text.data_ptr();
+  A.offs = (long long*)offs.data_ptr();
+  launch("format_emit", emit[variant], grid, dim3(FMT_BLOCK), 0, A);
+  return std::make_tuple(text, offs);
 }
 
 // Tagged point lines to rows (parse_points.h): text uint8 [data_len + 9],

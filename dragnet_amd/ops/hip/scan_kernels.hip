@@ -26,7 +26,9 @@
 // encode_table.h (device only: a scan's tables to the merge's wire form),
 // render_points.h (device only: the merged rows as NDJSON point lines),
 // rank_strings.h (kernels device only: the dictionary's byte-order ranks),
-// parse_points.h (kernels device only: tagged point lines back to rows).
+// parse_points.h (kernels device only: tagged point lines back to rows),
+// format_numbers.h (device only: numbers as their JavaScript strings, over
+// the host-compilable dbl2dec.h).
 
 #include "common.h"
 #include <hip/hip_runtime.h>
@@ -625,5 +627,8 @@ __global__ void extract_numdict_kernel(NumDict D, double* out_vals,
 
 // tagged point lines back to the rows the merge groups; last again
 #include "parse_points.h"
+
+// f64 values as their JavaScript strings, a blob with offsets; last again
+#include "format_numbers.h"
 
 }  // extern "C++"
